@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the Text2Human sampling hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config parsing|pose|hires]
+    python bench.py --gpus N --steps K --warmup W [--config parsing|pose|hires] [--dump-outputs DIR] [--full]
 
 One "step" = one full pass of the hot path over one batch of synthetic inputs per GPU, all
 inputs resident in HBM before the timed region:
@@ -14,7 +14,17 @@ inputs resident in HBM before the timed region:
   hires   (configs[4]): the 1024x512 upscaled hierarchy (SURVEY.md 8(d) interpretation: sample at
           32x16, nearest-x2 both quantised latents, fully-convolutional decode), batch 8 per GPU.
 
-The default run (`--config parsing`) also times, inside the same command, the other
+A plain run does only what the headline needs: set up, W warm-up steps, K timed steps, the outputs of the last timed
+step written to DIR with --dump-outputs, and the result line (metric, value, unit, ms_per_step, dtype, the per-stage
+times of the timed steps).  Everything else it measures or checks runs only with --full (below: roofline, parity,
+exact_fp32_path, fp16_planes_path, eager_launches, cpu_baseline, eager_gpu_baseline, other_configs).
+
+--dump-outputs DIR: what the last timed step returned to its caller, as float32 .npy files: `tokens` (the sampled top
+indices, [B, 18, 512]), `image` (the float image, [B, 3, H, W]) and `image_u8` ([B, H, W, 3]); rank r of an N-rank run
+writes its own shard with the suffix `_rank<r>`.  Above 64 MB in all, a fixed seeded subset of the batch rows is kept
+(the same rows in every file, listed in `sample_rows.npy`).
+
+The --full run (`--config parsing`) also times, inside the same command, the other
 configurations for 1 warm-up + 5 steps each and reports them under "other_configs": configs[3]'s
 per-GPU share (sample_from_parsing at 32 images per GPU; its global batch at N = 8 IS configs[3]),
 and at N = 1 configs[2] (pose, B = 32) and configs[4]'s per-GPU share (hires, B = 8).
@@ -25,7 +35,7 @@ equal --gpus), or plain `python bench.py --gpus N` spawns its own N ranks under 
 (weak scaling: the headline line keeps configs[1]'s 8 images per GPU at every N,
 "other_configs.parsing_b32" keeps 32 per GPU); weights are synthesised on rank 0 and broadcast over RCCL.
 
-Rank 0 prints ONE JSON line (contract in the task statement) including
+Rank 0 prints ONE JSON line (contract in the task statement); with --full it also carries
   roofline     -- dominant kernel (the split-precision GEMM of the sampler Linears: per fp32 multiply the fp16
                   hi*hi product + both cross terms in one 8-bit instruction on x8 operands; three fp16
                   products with T2H_X8=0) measured live with HIP events that receive the kernel's own
@@ -114,6 +124,12 @@ def parse_args(argv=None):
     ap.add_argument('--config', choices=['parsing', 'pose', 'hires'], default='parsing')
     ap.add_argument('--batch', type=int, default=0, help='images per GPU per step (0 = the config default)')
     ap.add_argument('--sample-steps', type=int, default=256)
+    ap.add_argument('--full', action='store_true',
+                    help='also run every measurement beside the headline: the individual-launches leg and its roofline, '
+                         'other_configs, cpu_baseline, exact_fp32_path + parity, fp16_planes_path, eager_gpu_baseline '
+                         '(each still switched off by its --no-* option)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the outputs of the last timed step as float32 .npy files into DIR')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-sampler-steps', type=int, default=32)
     ap.add_argument('--cpu-repeats', type=int, default=3)
@@ -659,7 +675,8 @@ class ConfigRun:
         else:
             mark('tokenizer', lambda: model.feed_data(batch))
         top = mark('sampler', lambda: model.sample_fn(temp=1, sample_steps=self.sample_steps))
-        _, u8 = mark('refine_decode', lambda: model.decode_indices(top, want_u8=True, upscale=self.upscale))
+        img, u8 = mark('refine_decode', lambda: model.decode_indices(top, want_u8=True, upscale=self.upscale))
+        self.last_img = img  # (the float image the caller also receives: --dump-outputs)
         return top, u8
 
     def timed(self, steps, warmup, dworld, dev):
@@ -692,7 +709,7 @@ class ConfigRun:
             stage_ms[name] = stage_ms.get(name, 0.0) + e0.elapsed_time(e1) / steps
         net = getattr(self.model, 'sampler_fn', None)
         step_ms = sorted(a.elapsed_time(b) for a, b in zip(marks[:-1], marks[1:]))
-        return dict(elapsed=elapsed, my_elapsed=my_elapsed, top=top, u8=u8, stage_ms=stage_ms,
+        return dict(elapsed=elapsed, my_elapsed=my_elapsed, top=top, u8=u8, img=self.last_img, stage_ms=stage_ms,
                     step_ms_median=(step_ms[len(step_ms) // 2] if step_ms else None),
                     step_ms_min_max=([step_ms[0], step_ms[-1]] if step_ms else None),
                     stats=getattr(net, 'last_stats', None), launch_mode=getattr(net, 'last_launch_mode', None))
@@ -799,6 +816,32 @@ def side_config(name, run, steps, warmup, batch_per_gpu, world, dworld, dev, pro
         out['eager_launches_ms_per_step'] = e['ms_per_step']
     return out
 
+
+
+# --------------------------------------------------------------------------- --dump-outputs
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, top, img, u8, suffix=''):
+    """The arrays the last timed step handed its caller, batch-major float32 -> out_dir/<name><suffix>.npy:
+    tokens [B, 18, 512] (the sampled top indices), image [B, 3, H, W] (None for the stub model), image_u8 [B, H, W, 3].
+    Over DUMP_LIMIT_BYTES in all, the same seeded subset of batch rows is kept in every file (sample_rows<suffix>.npy).
+    -> {name: shape written}."""
+    import numpy as np
+    arrays = {'tokens': torch.stack([t.reshape(t.shape[0], -1) for t in top], 1), 'image': img, 'image_u8': u8}
+    arrays = {k: v.detach().to('cpu', torch.float32).numpy() for k, v in arrays.items() if v is not None}
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    if total > DUMP_LIMIT_BYTES:
+        b = next(iter(arrays.values())).shape[0]
+        keep = max(1, b * DUMP_LIMIT_BYTES // total)
+        rows = np.sort(np.random.default_rng(2021).choice(b, keep, replace=False))
+        arrays = {k: np.ascontiguousarray(a[rows]) for k, a in arrays.items()}
+        np.save(os.path.join(out_dir, f'sample_rows{suffix}.npy'), rows.astype(np.float64))
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f'{k}{suffix}.npy'), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
 
 
 # --------------------------------------------------------------------------- the contract line
@@ -998,17 +1041,20 @@ def main(argv=None):
     hw = (1024, 512) if run.upscale else (512, 256)
     assert tuple(u8.shape) == (n_mine, hw[0], hw[1], 3), tuple(u8.shape)
     per_rank_ms = shard.gather_floats(1000.0 * res['my_elapsed'] / args.steps, dworld, dev)
+    dumped = None
+    if args.dump_outputs:  # before any further leg reuses the model's buffers
+        dumped = dump_outputs(args.dump_outputs, top, res['img'], u8, suffix=f'_rank{rank}' if world > 1 else '')
     # ---- the same step as individual launches, with the per-launch event sampling armed (outside the headline's
     # timed region, no collective: every rank runs it on its own)
     eager = None
-    if not stub and not args.no_eager_leg:
+    if not stub and args.full and not args.no_eager_leg:
         eager = run.eager_profile(max(1, args.eager_steps))
     # a checksum of every rank's images reaches rank 0 (the optional image gather of SURVEY 8(e))
     sums = shard.gather_floats(float(u8.to(torch.float64).sum()), dworld, dev)
 
     # ---- the other BASELINE.json configurations, inside the same (driver-run) command
     other = {}
-    if args.config == 'parsing' and not args.no_other_configs and (stub or not args.batch):
+    if args.full and args.config == 'parsing' and not args.no_other_configs and (stub or not args.batch):
         # configs[3]'s per-GPU share (batch 256 over 8 GPUs = 32 per GPU) at every N: at N = 8 its global
         # batch IS configs[3]; the headline line above keeps configs[1]'s 8 per GPU at every N (weak scaling)
         # (--stub-model: the same leg with a small batch, so that its collectives run under gloo in the tests)
@@ -1074,7 +1120,10 @@ def main(argv=None):
         'per_rank_image_checksum': sums,
         'weights_s': t_weights,
         'launch_thread_cores': pinned,
+        'full': args.full,
     }
+    if dumped is not None:
+        out['dumped_outputs'] = dumped
     if stub:
         if other:
             out['other_configs'] = other
@@ -1114,6 +1163,11 @@ def main(argv=None):
     out['path_tflops'] = per_image * out['value'] / world
     if other:
         out['other_configs'] = other
+    if not args.full:
+        emit(out)
+        if use_dist:
+            dist.destroy_process_group()
+        return
     if world == 1 and not args.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline(args.sample_steps, args.cpu_sampler_steps, args.cpu_repeats)
     if world == 1 and not args.no_exact_fp32 and split_on:

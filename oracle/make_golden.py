@@ -232,9 +232,65 @@ def main():
             attr_embedding=emb.numpy(), segm=lg.argmax(1).numpy().astype(np.int8),
             margin=(t2[:, 0] - t2[:, 1]).numpy(),
             logits_sample=lg[:, :, ::8, ::8].numpy(), logits_moments=moments(lg))
+    make_dataset_golden()
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))
 
 
+DATASET_GOLDEN = os.path.join(OUT, 'dataset_loaders_ref.json')
+
+
+def dataset_item_record(item):
+    """One dataset item as {key: value} with every array replaced by its kind, dtype, shape and the sha256 of its bytes:
+    equal records <=> equal items (torch.equal / np.array_equal, same dtype)."""
+    import hashlib
+    rec = {}
+    for k, v in item.items():
+        if torch.is_tensor(v) or isinstance(v, np.ndarray):
+            a = v.detach().contiguous().numpy() if torch.is_tensor(v) else np.ascontiguousarray(v)
+            rec[k] = {'kind': 'torch' if torch.is_tensor(v) else 'numpy', 'dtype': str(a.dtype), 'shape': list(a.shape),
+                      'sha256': hashlib.sha256(a.tobytes()).hexdigest()}
+        else:
+            rec[k] = v.item() if isinstance(v, np.generic) else v
+    return rec
+
+
+def make_dataset_golden(ref_data_dir=None):
+    """The reference's own dataset readers (data/segm_attr_dataset.py, data/pose_attr_dataset.py) on the synthetic
+    DeepFashion tree of tests/test_data.py (synthetic.write_dataset_tree, n=3, seed 7) -> tests/golden/
+    dataset_loaders_ref.json (records of dataset_item_record)."""
+    import importlib.util
+    import json
+    import tempfile
+
+    def load(name):
+        spec = importlib.util.spec_from_file_location(f'ref_{name}', os.path.join(ref_data_dir, f'{name}.py'))
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        return mod
+
+    if ref_data_dir is None:  # (the reference's source tree, where oracle/make_ref.py compiles from)
+        from oracle import make_ref
+        ref_data_dir = os.path.join(make_ref.SRC, 'data')
+    with tempfile.TemporaryDirectory() as d:
+        tree = synthetic.write_dataset_tree(d, n=3, seed=7)
+        segm = load('segm_attr_dataset').DeepFashionAttrSegmDataset(
+            img_dir=tree['test_img_dir'], segm_dir=tree['segm_dir'], pose_dir=tree['pose_dir'],
+            ann_dir=tree['test_ann_file'])
+        pose = load('pose_attr_dataset').DeepFashionAttrPoseDataset(
+            pose_dir=tree['pose_dir'], texture_ann_dir=tree['texture_ann_file'], shape_ann_path=tree['shape_ann_path'])
+        out = {'tree': {'n': 3, 'seed': 7},
+               'segm_attr_dataset': [dataset_item_record(segm[i]) for i in range(len(segm))],
+               'pose_attr_dataset': [dataset_item_record(pose[i]) for i in range(len(pose))]}
+    with open(DATASET_GOLDEN, 'w') as f:
+        json.dump(out, f, indent=1)
+        f.write('\n')
+    return out
+
+
 if __name__ == '__main__':
-    main()
+    import sys
+    if sys.argv[1:] == ['datasets']:  # python -m oracle.make_golden datasets: the dataset records alone
+        make_dataset_golden()
+    else:
+        main()

@@ -3,11 +3,11 @@
 Loads the *unmodified* reference (yumingj/Text2Human) so that (a) the CPU
 restatement in ``oracle/torch_ref.py`` can be validated against it, (b)
 ``oracle/make_golden.py`` can emit golden vectors and (c) ``bench.py``'s
-``cpu_baseline`` times the reference itself.  From ``/root/reference`` (the
-sources, build container) or, where that does not exist (the GPU box), from the
-byte code ``oracle/make_ref.py`` compiled from those sources into the git-ignored
-``oracle/_ref/`` -- the same modules, no source copied.  Nothing at run time reads
-``/root/reference`` on the GPU box.
+``cpu_baseline`` times the reference itself.  From the byte code
+``oracle/make_ref.py`` compiled from the reference's sources into the git-ignored
+``oracle/_ref/`` (``build()``) -- the same modules, no source copied -- and only
+where that is absent from the reference's source tree.  Nothing at run time reads
+the reference's source tree once ``build()`` has compiled it.
 
 The reference hard-imports packages that are absent offline (mmcv, mmseg,
 torchvision, lpips) and hard-codes ``torch.device('cuda')``
@@ -51,6 +51,8 @@ def _pick_root():
     env = os.environ.get('T2H_REFERENCE_ROOT')
     if env:
         return env
+    if _bytecode_ok(BYTECODE_ROOT):  # what build() compiled into this tree: tests read nothing outside it
+        return BYTECODE_ROOT
     if os.path.isdir('/root/reference/models/archs'):
         return '/root/reference'
     return BYTECODE_ROOT

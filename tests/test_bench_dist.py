@@ -24,7 +24,7 @@ def _run(nproc, extra=()):
     env = dict(os.environ, T2H_NO_PIN='0', OMP_NUM_THREADS='1')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', f'--nproc-per-node={nproc}',
            '--master-addr', '127.0.0.1', '--master-port', str(_free_port()), os.path.join(ROOT, 'bench.py'),
-           '--gpus', str(nproc), '--steps', '3', '--warmup', '1', '--stub-model', '--batch', '3', *extra]
+           '--gpus', str(nproc), '--steps', '3', '--warmup', '1', '--stub-model', '--batch', '3', '--full', *extra]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -90,6 +90,57 @@ def test_plain_python_bench_gpus_2_spawns_its_own_ranks():
     out = json.loads(lines[0])
     assert out['n_gpus'] == 2 and out['rccl_world'] == 2 and out['config']['global_batch'] == 6
     assert len(out['per_rank_ms_per_step']) == 2
+
+
+@pytest.mark.timeout(300)
+def test_plain_run_is_the_headline_alone_and_dumps_its_last_step(tmp_path):
+    """Without --full only the headline is measured (no other_configs leg); --dump-outputs DIR writes what the last timed
+    step returned as float32 .npy files, and the same arguments give the same arrays."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'LOCAL_WORLD_SIZE',
+                                                             'MASTER_ADDR', 'MASTER_PORT', 'T2H_FORCE_DIST')}
+    env.update(T2H_NO_PIN='0', OMP_NUM_THREADS='1')
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f'run{i}'
+        cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+               '--stub-model', '--batch', '3', '--dump-outputs', str(d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        out = json.loads(lines[0])
+        assert out['steps'] == 3 and out['warmup'] == 1 and out['ms_per_step'] > 0
+        assert abs(out['value'] - 3 * 1000.0 / out['ms_per_step']) < 1e-6 * out['value']
+        assert 'other_configs' not in out and 'cpu_baseline' not in out
+        assert sorted(p.name for p in d.iterdir()) == ['image_u8.npy', 'tokens.npy']
+        a = {n: np.load(d / f'{n}.npy') for n in ('tokens', 'image_u8')}
+        assert all(v.dtype == np.float32 for v in a.values())
+        assert a['tokens'].shape == (3, 1, 4) and a['image_u8'].shape == (3, 512, 256, 3)
+        dumps.append(a)
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n
+
+
+def test_dump_outputs_keeps_a_seeded_subset_of_rows_above_the_limit(tmp_path, monkeypatch):
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    top = [torch.arange(8 * 512).view(8, 512) % 1024 for _ in range(18)]
+    img = torch.rand(8, 3, 64, 32)
+    u8 = (img.permute(0, 2, 3, 1) * 255).to(torch.uint8)
+    full = bench.dump_outputs(str(tmp_path / 'all'), top, img, u8)
+    assert full == {'tokens': [8, 18, 512], 'image': [8, 3, 64, 32], 'image_u8': [8, 64, 32, 3]}
+    assert np.array_equal(np.load(tmp_path / 'all' / 'image.npy'), img.numpy())
+    assert np.array_equal(np.load(tmp_path / 'all' / 'tokens.npy'), torch.stack(top, 1).float().numpy())
+    monkeypatch.setattr(bench, 'DUMP_LIMIT_BYTES', 200_000)
+    for run in ('a', 'b'):
+        part = bench.dump_outputs(str(tmp_path / run), top, img, u8)
+        size = sum(np.load(tmp_path / run / f'{n}.npy').nbytes for n in part)
+        assert size <= 200_000 and part['image'][0] == part['tokens'][0] < 8
+    rows = np.load(tmp_path / 'a' / 'sample_rows.npy').astype(np.int64)
+    assert np.array_equal(rows, np.load(tmp_path / 'b' / 'sample_rows.npy'))
+    assert np.array_equal(np.load(tmp_path / 'a' / 'image_u8.npy'), u8.numpy()[rows].astype(np.float32))
 
 
 def test_a_launcher_whose_world_size_differs_from_gpus_is_refused():

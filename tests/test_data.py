@@ -1,16 +1,17 @@
 """Dataset readers on a tiny synthetic DeepFashion-style tree: item
-contract, and -- where /root/reference exists -- equality with the reference's own loaders."""
-import importlib.util
+contract, and equality with the reference's own loaders (their items, recorded in tests/golden/)."""
+import json
 import os
 
 import numpy as np
 import pytest
 import torch
 
+from oracle.make_golden import dataset_item_record
 from text2human_amd import synthetic
 from text2human_amd.data import DeepFashionAttrPoseDataset, DeepFashionAttrSegmDataset, deepfashion
 
-REF = '/root/reference/data'
+GOLD = os.path.join(os.path.dirname(__file__), 'golden', 'dataset_loaders_ref.json')
 
 
 @pytest.fixture(scope='module')
@@ -56,33 +57,20 @@ def test_annotation_files_must_agree(tree, tmp_path):
         deepfashion.read_fused_annotations(str(bad))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference tree absent')
 def test_items_equal_the_reference_loaders(tree):
-    def load(name):
-        spec = importlib.util.spec_from_file_location(f'ref_{name}', os.path.join(REF, f'{name}.py'))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        return mod
-
+    """Every item of both readers equals, key for key and byte for byte, what the reference's own readers
+    (data/segm_attr_dataset.py, data/pose_attr_dataset.py) return on the same tree: their records are stored in
+    tests/golden/dataset_loaders_ref.json (oracle/make_golden.py `datasets`)."""
+    gold = json.load(open(GOLD))
+    assert gold['tree'] == {'n': 3, 'seed': 7}
     ours = DeepFashionAttrSegmDataset(img_dir=tree['test_img_dir'], segm_dir=tree['segm_dir'],
                                       pose_dir=tree['pose_dir'], ann_dir=tree['test_ann_file'])
-    ref = load('segm_attr_dataset').DeepFashionAttrSegmDataset(
-        img_dir=tree['test_img_dir'], segm_dir=tree['segm_dir'], pose_dir=tree['pose_dir'],
-        ann_dir=tree['test_ann_file'])
-    assert len(ours) == len(ref)
-    for i in range(len(ref)):
-        a, b = ours[i], ref[i]
-        assert a.keys() == b.keys() and a['img_name'] == b['img_name']
-        for k in ('image', 'segm', 'texture_mask'):
-            assert torch.equal(a[k], b[k]) and a[k].dtype == b[k].dtype, k
-        assert np.array_equal(a['densepose'], b['densepose'])
     ours_p = DeepFashionAttrPoseDataset(pose_dir=tree['pose_dir'], texture_ann_dir=tree['texture_ann_file'],
                                         shape_ann_path=tree['shape_ann_path'])
-    ref_p = load('pose_attr_dataset').DeepFashionAttrPoseDataset(
-        pose_dir=tree['pose_dir'], texture_ann_dir=tree['texture_ann_file'], shape_ann_path=tree['shape_ann_path'])
-    for i in range(len(ref_p)):
-        a, b = ours_p[i], ref_p[i]
-        assert a.keys() == b.keys()
-        assert np.array_equal(a['densepose'], b['densepose']) and torch.equal(a['shape_attr'], b['shape_attr'])
-        for k in ('img_name', 'upper_fused_attr', 'lower_fused_attr', 'outer_fused_attr'):
-            assert a[k] == b[k]
+    for ds, ref in ((ours, gold['segm_attr_dataset']), (ours_p, gold['pose_attr_dataset'])):
+        assert len(ds) == len(ref)
+        for i in range(len(ref)):
+            a = dataset_item_record(ds[i])
+            assert a.keys() == ref[i].keys()
+            for k in ref[i]:
+                assert a[k] == ref[i][k], (type(ds).__name__, i, k)

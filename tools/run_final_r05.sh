@@ -25,7 +25,7 @@ echo "tests exit $? ($(( $(date +%s) - S )) s)" | tee -a $OUT/gpu_tests_decode_s
 tail -6 $OUT/gpu_tests_decode_side.log
 if [ "${ONLY_TESTS:-0}" = "1" ]; then exit 0; fi
 S=$(date +%s)
-python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_cmd.json 2> $OUT/bench_driver_cmd.err
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_driver_cmd.json 2> $OUT/bench_driver_cmd.err
 echo "bench wall $(( $(date +%s) - S )) s" | tee $OUT/bench_driver_cmd.wall
 cp gpurun_out/bench_detail.json $OUT/bench_driver_cmd_detail.json
 tail -c 3000 $OUT/bench_driver_cmd.json

@@ -11,7 +11,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 cd $REPO
 S=$(date +%s)
-python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_cmd.json 2> $OUT/bench_driver_cmd.err
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_driver_cmd.json 2> $OUT/bench_driver_cmd.err
 echo "bench wall $(( $(date +%s) - S )) s" | tee $OUT/bench_driver_cmd.wall
 cp gpurun_out/bench_detail.json $OUT/bench_driver_cmd_detail.json
 tail -c 3200 $OUT/bench_driver_cmd.json

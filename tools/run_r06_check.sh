@@ -19,7 +19,7 @@ T2H_GPU_SUITE_BUDGET_S=0 timeout 1500 python -m pytest tests -q -m gpu --duratio
 echo "suite exit $? ($(( $(date +%s) - S )) s)" | tee -a $OUT/gpu_suite.log
 tail -90 $OUT/gpu_suite.log
 S=$(date +%s)
-python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_cmd.json 2> $OUT/bench_driver_cmd.err
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_driver_cmd.json 2> $OUT/bench_driver_cmd.err
 echo "bench exit $? wall $(( $(date +%s) - S )) s" | tee $OUT/bench_driver_cmd.wall
 cp gpurun_out/bench_detail.json $OUT/bench_driver_cmd_detail.json
 tail -c 3200 $OUT/bench_driver_cmd.json
