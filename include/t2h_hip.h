@@ -386,6 +386,28 @@ int t2h_philox_uniform_f32(uint64_t seed, uint64_t offset, uint32_t grid_threads
 int t2h_unmask_schedule(uint64_t seed, uint64_t offset, uint32_t rand_grid_threads, uint32_t rand_inc,
                         uint32_t expo_inc, const int64_t* tex, int32_t n, int32_t steps, int32_t n_heads,
                         int32_t* step_of_row, uint32_t* head_mask, void* stream);
+/* Region editing ("Editing a region"): the same loop started from a partially known state.
+ * t2h_unmask_schedule_keep: t2h_unmask_schedule with keep[n] (uint8): kept rows start unmasked, are never drawn,
+ *   set no head bit and get step_of_row = 0; the rand draws and the offset recurrence are the same
+ *   (keep all zero -> the bits of t2h_unmask_schedule).
+ * t2h_edit_prefill: x_t[i] = keep[i] ? src[tex[i]][i] + n_class * tex[i] : mask_id, out_lists[h][i] = src[h][i] if
+ *   keep[i] and tex[i] == h, else -1 (src / out_lists [n_heads][n]).  A kept row whose source token is not in
+ *   [0, n_class) sets *err = max(*err, n - i): the first such row is n - *err (the caller zeroes *err; 0 = none).
+ *   x_t and out_lists may be NULL (check only).
+ * t2h_region_keep: keep[B][th * tw] = 0 iff ANY pixel of the token's (H / th) x (W / tw) cell lies in the region,
+ *   else 1.  mode 0: mask_u8 [B][H][W], nonzero = region; mode 1: map_f32 [B][H][W], nonzero = region; mode 2:
+ *   map_f32 = parsing map (class ids as floats), region = the ids whose bit is set in label_bits.
+ * t2h_merge_kept_indices: dst[h][r] = src[h][r] where keep[r] ([n_heads][n] int64). */
+int t2h_unmask_schedule_keep(uint64_t seed, uint64_t offset, uint32_t rand_grid_threads, uint32_t rand_inc,
+                             uint32_t expo_inc, const int64_t* tex, const uint8_t* keep, int32_t n, int32_t steps,
+                             int32_t n_heads, int32_t* step_of_row, uint32_t* head_mask, void* stream);
+int t2h_edit_prefill(const int64_t* src_lists, const int64_t* tex, const uint8_t* keep, int64_t mask_id,
+                     int64_t* x_t, int64_t* out_lists, uint32_t* err, int32_t n, int32_t n_heads, int32_t n_class,
+                     void* stream);
+int t2h_region_keep(const uint8_t* mask_u8, const float* map_f32, uint64_t label_bits, int32_t mode, int32_t B,
+                    int32_t H, int32_t W, int32_t th, int32_t tw, uint8_t* keep, void* stream);
+int t2h_merge_kept_indices(const int64_t* src_lists, const uint8_t* keep, int64_t* dst_lists, int32_t n,
+                           int32_t n_heads, void* stream);
 /* Round cursor of a schedule laid out as padded tables [rounds][maxr] (a round's list padded with
  * copies of one of its own rows: sampling a row twice writes the same token twice): copies round
  * r = *round_ctr of rows_tbl (and of aux64_tbl = per-row generator offsets / aux32_tbl = per-row explicit

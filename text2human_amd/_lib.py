@@ -111,6 +111,12 @@ SIGNATURES = {
     't2h_philox_uniform_f32': (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, c_vp, c_i64, c_vp]),
     't2h_unmask_schedule': (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
                                            ctypes.c_uint32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    't2h_unmask_schedule_keep': (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                                ctypes.c_uint32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    't2h_edit_prefill': (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
+    't2h_region_keep': (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp,
+                                       c_vp]),
+    't2h_merge_kept_indices': (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]),
     't2h_schedule_advance': (ctypes.c_int, [c_vp] * 7 + [c_i32, c_vp]),
     't2h_q_sample': (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_vp, c_vp, c_i32, c_i32, c_vp]),
     't2h_masked_ce_heads': (ctypes.c_int, [c_vp] * 9 + [c_i32] * 5 + [c_vp]),

@@ -369,11 +369,14 @@ __global__ void philox_uniform_kernel(uint64_t seed, uint64_t offset, uint32_t g
 // One workgroup (the steps are sequential and a step is n / 1024 Philox blocks per thread);
 // outputs: step_of_row[i] = the step at which token row i changes (every row changes exactly once:
 // at t = 1 the threshold is 1), head_mask[t] = bit h set iff head h samples at step t.
+// KEEP (region editing, t2h_unmask_schedule_keep): rows with keep[i] != 0 start unmasked -- they are never drawn,
+// never set a head bit and keep step_of_row = 0; the `rand` draws and the offset recurrence are unchanged.
 constexpr int SCHED_THREADS = 1024, SCHED_MAX_STEPS = 4096;
+template <bool KEEP>
 __global__ __launch_bounds__(SCHED_THREADS) void unmask_schedule_kernel(
     uint64_t seed, uint64_t offset, uint32_t rand_grid_threads, uint32_t rand_inc, uint32_t expo_inc,
-    const int64_t* __restrict__ tex, int n, int steps, int32_t* __restrict__ step_of_row,
-    uint32_t* __restrict__ head_mask) {
+    const int64_t* __restrict__ tex, const uint8_t* __restrict__ keep, int n, int steps,
+    int32_t* __restrict__ step_of_row, uint32_t* __restrict__ head_mask) {
   __shared__ uint32_t mask_s[SCHED_MAX_STEPS + 1];  // one word per step: no reset, one barrier per step
   const int tid = threadIdx.x, lane = tid & 63;
   for (int e = tid; e < n; e += SCHED_THREADS) step_of_row[e] = 0;
@@ -385,6 +388,7 @@ __global__ __launch_bounds__(SCHED_THREADS) void unmask_schedule_kernel(
     uint32_t m = 0;
     for (int e = tid; e < n; e += SCHED_THREADS) {
       if (step_of_row[e] != 0) continue;  // already unmasked (written by this same thread)
+      if (KEEP && keep[e] != 0) continue;  // kept row: unmasked from the start
       if (torch_uniform_at(seed, off, rand_grid_threads, (uint64_t)e) < thresh) {
         step_of_row[e] = t;
         m |= 1u << (int)tex[e];
@@ -397,6 +401,68 @@ __global__ __launch_bounds__(SCHED_THREADS) void unmask_schedule_kernel(
     off += (uint64_t)rand_inc + (uint64_t)__popc(mask_s[t]) * expo_inc;
   }
   for (int t = tid; t <= steps; t += SCHED_THREADS) head_mask[t] = mask_s[t];
+}
+
+// ---- region editing: the reference loop started from a partially known state ("Editing a region").
+// Prefill: kept rows (keep[i] != 0) start as their source token src[tex[i]][i] (+ n_class * tex[i] in x_t), every
+// other row masked; out_lists[h][i] = the kept token where h == tex[i], else -1.  A kept row without a valid source
+// token under its texture (-1, or outside [0, n_class)) raises the error word: err = max(err, n - i), so the host reads
+// the FIRST such row as n - err (err == 0: none; the host zeroes it).  x_t / out_lists may be NULL (check only).
+__global__ void edit_prefill_kernel(const int64_t* __restrict__ src, const int64_t* __restrict__ tex,
+                                    const uint8_t* __restrict__ keep, int64_t mask_id, int64_t* __restrict__ x_t,
+                                    int64_t* __restrict__ out, uint32_t* __restrict__ err, int n, int n_heads,
+                                    int n_class) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int h = (int)tex[i];
+  const bool k = keep[i] != 0;
+  const int64_t v = (k && h >= 0 && h < n_heads) ? src[(int64_t)h * n + i] : -1;
+  const bool ok = v >= 0 && v < n_class;
+  if (k && !ok) atomicMax(err, (uint32_t)(n - i));
+  const bool kept = k && ok;
+  if (x_t) x_t[i] = kept ? v + (int64_t)n_class * h : mask_id;
+  if (out)
+    for (int j = 0; j < n_heads; ++j) out[(int64_t)j * n + i] = (kept && j == h) ? v : -1;
+}
+
+// Region -> keep: one wave per token cell (th x tw cells of (H / th) x (W / tw) pixels); the cell is resampled
+// (keep = 0) iff ANY of its pixels is in the region.  mode 0: uint8 mask, nonzero = region; mode 1: fp32 mask,
+// nonzero = region; mode 2: fp32 parsing map, region = the labels whose bit is set in label_bits (ids 0..63).
+constexpr int RK_CELLS = 4;  // cells (waves) per workgroup
+__global__ __launch_bounds__(64 * RK_CELLS) void region_keep_kernel(const uint8_t* __restrict__ mask_u8,
+                                                                  const float* __restrict__ map_f32,
+                                                                  uint64_t label_bits, int mode, int H, int W, int th,
+                                                                  int tw, int n_cells, uint8_t* __restrict__ keep) {
+  const int lane = threadIdx.x & 63;
+  const int cell = blockIdx.x * RK_CELLS + (threadIdx.x >> 6);
+  if (cell >= n_cells) return;  // (uniform over the wave)
+  const int T = th * tw, b = cell / T, c = cell - b * T, ci = c / tw, cj = c - ci * tw;
+  const int ch = H / th, cw = W / tw;
+  int hit = 0;
+  for (int p = lane; p < ch * cw; p += 64) {
+    const int y = ci * ch + p / cw, x = cj * cw + p % cw;
+    const int64_t q = ((int64_t)b * H + y) * W + x;
+    if (mode == 0) {
+      hit |= mask_u8[q] != 0;
+    } else if (mode == 1) {
+      hit |= map_f32[q] != 0.f;
+    } else {
+      const float v = map_f32[q];
+      const int l = (int)v;
+      hit |= (v >= 0.f && v < 64.f && (float)l == v && ((label_bits >> l) & 1ull)) ? 1 : 0;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) hit |= __shfl_xor(hit, o, 64);
+  if (lane == 0) keep[cell] = hit ? 0 : 1;
+}
+
+// dst[h][r] = src[h][r] where keep[r] (bottom indices of an edited photo: the encoder's outside the region)
+__global__ void merge_kept_kernel(const int64_t* __restrict__ src, const uint8_t* __restrict__ keep,
+                                  int64_t* __restrict__ dst, int n, int64_t total) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  if (keep[i % n]) dst[i] = src[i];
 }
 
 // ---- round cursor of a pre-computed schedule (engine.sample_tokens, graph replay): copies round
@@ -695,9 +761,59 @@ extern "C" int t2h_unmask_schedule(uint64_t seed, uint64_t offset, uint32_t rand
   T2H_REQUIRE(n > 0 && steps >= 1 && steps <= SCHED_MAX_STEPS && n_heads > 0 && n_heads <= T2H_MAX_HEADS &&
                   rand_grid_threads > 0 && offset % 4 == 0 && rand_inc % 4 == 0 && expo_inc % 4 == 0,
               "t2h_unmask_schedule: bad arguments (n=%d steps=%d n_heads=%d)", n, steps, n_heads);
-  hipLaunchKernelGGL(unmask_schedule_kernel, dim3(1), dim3(SCHED_THREADS), 0, static_cast<hipStream_t>(stream), seed,
-                     offset, rand_grid_threads, rand_inc, expo_inc, tex, n, steps, step_of_row, head_mask);
+  hipLaunchKernelGGL(unmask_schedule_kernel<false>, dim3(1), dim3(SCHED_THREADS), 0, static_cast<hipStream_t>(stream),
+                     seed, offset, rand_grid_threads, rand_inc, expo_inc, tex, (const uint8_t*)nullptr, n, steps,
+                     step_of_row, head_mask);
   T2H_CHECK_LAUNCH("t2h_unmask_schedule");
+  return T2H_OK;
+}
+
+extern "C" int t2h_unmask_schedule_keep(uint64_t seed, uint64_t offset, uint32_t rand_grid_threads, uint32_t rand_inc,
+                                        uint32_t expo_inc, const int64_t* tex, const uint8_t* keep, int32_t n,
+                                        int32_t steps, int32_t n_heads, int32_t* step_of_row, uint32_t* head_mask,
+                                        void* stream) {
+  T2H_REQUIRE(tex && keep && step_of_row && head_mask, "t2h_unmask_schedule_keep: NULL pointer");
+  T2H_REQUIRE(n > 0 && steps >= 1 && steps <= SCHED_MAX_STEPS && n_heads > 0 && n_heads <= T2H_MAX_HEADS &&
+                  rand_grid_threads > 0 && offset % 4 == 0 && rand_inc % 4 == 0 && expo_inc % 4 == 0,
+              "t2h_unmask_schedule_keep: bad arguments (n=%d steps=%d n_heads=%d)", n, steps, n_heads);
+  hipLaunchKernelGGL(unmask_schedule_kernel<true>, dim3(1), dim3(SCHED_THREADS), 0, static_cast<hipStream_t>(stream),
+                     seed, offset, rand_grid_threads, rand_inc, expo_inc, tex, keep, n, steps, step_of_row, head_mask);
+  T2H_CHECK_LAUNCH("t2h_unmask_schedule_keep");
+  return T2H_OK;
+}
+
+extern "C" int t2h_edit_prefill(const int64_t* src_lists, const int64_t* tex, const uint8_t* keep, int64_t mask_id,
+                                int64_t* x_t, int64_t* out_lists, uint32_t* err, int32_t n, int32_t n_heads,
+                                int32_t n_class, void* stream) {
+  T2H_REQUIRE(src_lists && tex && keep && err, "t2h_edit_prefill: NULL pointer");
+  T2H_REQUIRE(n > 0 && n_heads > 0 && n_heads <= T2H_MAX_HEADS && n_class > 0, "t2h_edit_prefill: bad arguments");
+  hipLaunchKernelGGL(edit_prefill_kernel, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     src_lists, tex, keep, mask_id, x_t, out_lists, err, n, n_heads, n_class);
+  T2H_CHECK_LAUNCH("t2h_edit_prefill");
+  return T2H_OK;
+}
+
+extern "C" int t2h_region_keep(const uint8_t* mask_u8, const float* map_f32, uint64_t label_bits, int32_t mode,
+                               int32_t B, int32_t H, int32_t W, int32_t th, int32_t tw, uint8_t* keep, void* stream) {
+  T2H_REQUIRE(keep && (mode == 0 ? mask_u8 != nullptr : map_f32 != nullptr), "t2h_region_keep: NULL pointer");
+  T2H_REQUIRE(mode >= 0 && mode <= 2 && B > 0 && th > 0 && tw > 0 && H >= th && W >= tw && H % th == 0 &&
+                  W % tw == 0,
+              "t2h_region_keep: bad arguments (mode=%d H=%d W=%d cells %dx%d)", mode, H, W, th, tw);
+  const int n_cells = B * th * tw;
+  hipLaunchKernelGGL(region_keep_kernel, dim3((n_cells + RK_CELLS - 1) / RK_CELLS), dim3(64 * RK_CELLS), 0,
+                     static_cast<hipStream_t>(stream), mask_u8, map_f32, label_bits, mode, H, W, th, tw, n_cells, keep);
+  T2H_CHECK_LAUNCH("t2h_region_keep");
+  return T2H_OK;
+}
+
+extern "C" int t2h_merge_kept_indices(const int64_t* src_lists, const uint8_t* keep, int64_t* dst_lists, int32_t n,
+                                      int32_t n_heads, void* stream) {
+  T2H_REQUIRE(src_lists && keep && dst_lists, "t2h_merge_kept_indices: NULL pointer");
+  T2H_REQUIRE(n > 0 && n_heads > 0, "t2h_merge_kept_indices: bad arguments");
+  const int64_t total = (int64_t)n * n_heads;
+  hipLaunchKernelGGL(merge_kept_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), src_lists, keep, dst_lists, n, total);
+  T2H_CHECK_LAUNCH("t2h_merge_kept_indices");
   return T2H_OK;
 }
 

@@ -541,8 +541,9 @@ class SampleSchedule:
     rows[start[r]:start[r + 1]], each with its own noise reference."""
 
     def __init__(self, rows, start, round_steps, noise_kind, seed=None, offsets=None, expo_rows=None, slots=None,
-                 host=None, perm=None, rng_rows=None, active=None):
+                 host=None, perm=None, rng_rows=None, active=None, kept=None):
         self.rows, self.start, self.round_steps = rows, start, round_steps
+        self.kept = kept  # region editing: bool [B*T] (schedule order) of the rows that keep their source token
         self.host = host  # (row order, per-row offsets[, rng rows]) as numpy, for the padded tables of the graph path
         # finished samples leave the batch (schedule.leave_order): perm[new position] = original sample, rows /
         # round_steps are in the NEW order, rng_rows = the original row of every listed row (its noise), active[r] =
@@ -558,10 +559,24 @@ class SampleSchedule:
         return ('explicit', self.expo_rows, self.slots[lo:hi])
 
 
-def build_schedule(tex_tok, sample_steps, n_books, n_class, noise, compact=True, shrink=False):
+def _init_check(err, keep, T):
+    """Region editing: the kept rows as a host bool [B*T]; raises T2HError (naming the first offending (sample, row))
+    if a kept row has no source token under its texture -- t2h_edit_prefill's error word, read after the schedule's
+    own host read (the stream has drained by then)."""
+    e = int(err.cpu()[0])
+    if e:
+        r = keep.numel() - e
+        raise _lib.T2HError(f'region edit: token row {r % T} of sample {r // T} is kept but its source list holds no '
+                            'index under the current texture map (resample it, or give a source for that texture)')
+    return keep.cpu().numpy().astype(bool)
+
+
+def build_schedule(tex_tok, sample_steps, n_books, n_class, noise, compact=True, shrink=False, init=None):
     """The unmasking schedule + RNG bookkeeping of one sample_fn call (schedule.py), consuming
     `noise` exactly as the reference's loop would (models/sample_model.py:279-306).  shrink (compact rounds on the
-    device generator only): the samples are reordered so that finished ones leave the batch (SampleSchedule.perm)."""
+    device generator only): the samples are reordered so that finished ones leave the batch (SampleSchedule.perm).
+    init = (src_lists int64 [n_books, B*T], keep uint8 [B*T]) (region editing): the kept rows start unmasked and are
+    never drawn; a kept row without a source token raises T2HError before the generator has moved."""
     B, T = tex_tok.shape
     dev = tex_tok.device
     n = B * T
@@ -572,24 +587,32 @@ def build_schedule(tex_tok, sample_steps, n_books, n_class, noise, compact=True,
     # host copy the schedule needs anyway (no extra device read)
     if tex_host.size and (int(tex_host.min()) < 0 or int(tex_host.max()) >= n_books):
         raise _lib.T2HError(f'texture ids must lie in [0, {n_books}), got [{int(tex_host.min())}, {int(tex_host.max())}]')
+    keep = err = kept = None
+    if init is not None:
+        src_lists, keep = init
+        err = ops.edit_prefill(src_lists, tex_flat, keep, 0, n_class)  # (check only: the error word)
     if isinstance(noise, TorchDeviceNoise) and noise.emulation_ok(n, n_class):
         # one launch reproduces every `rand` draw; one host read fetches the whole schedule
         gen, _ = noise.generator()
         seed, off0 = gen.initial_seed(), gen.get_offset()
-        step_dev, mask_dev, rand_inc, expo_inc = ops.unmask_schedule(seed, off0, tex_flat, sample_steps, n_books, n_class)
+        step_dev, mask_dev, rand_inc, expo_inc = ops.unmask_schedule(seed, off0, tex_flat, sample_steps, n_books, n_class,
+                                                                     keep=keep)
         step_of_row = step_dev.cpu().numpy()
+        if init is not None:
+            kept = _init_check(err, keep, T)
         head_mask = mask_dev.cpu().numpy().astype(np.int64) & 0xFFFFFFFF
         _, expo_off, final = schedule.draw_offsets(head_mask, sample_steps, off0, rand_inc, expo_inc, n_books)
         gen.set_offset(final)  # where the reference's generator stands after its loop
         perm = rng_rows = rng_dev = active = None
         if shrink and compact and B > 1:
-            perm, _ = schedule.leave_order(step_of_row, B, T)
+            perm, _ = schedule.leave_order(step_of_row, B, T, kept)
             if (perm == np.arange(B)).all():
                 perm = None
         if perm is not None:
             orig_row = (perm[:, None] * T + np.arange(T)[None, :]).reshape(-1)  # original row of every reordered row
             step_of_row, tex_host = step_of_row[orig_row], tex_host[orig_row]
-        order, start, round_steps = schedule.group_rounds(step_of_row, B, T, compact)
+            kept = kept[orig_row] if kept is not None else None
+        order, start, round_steps = schedule.group_rounds(step_of_row, B, T, compact, kept)
         offs = expo_off[step_of_row[order], tex_host[order]]
         assert (offs >= 0).all()
         if shrink and compact:
@@ -600,10 +623,13 @@ def build_schedule(tex_tok, sample_steps, n_books, n_class, noise, compact=True,
             rng_dev = torch.from_numpy(rng_rows).to(dev)
         return SampleSchedule(torch.from_numpy(order.astype(np.int32)).to(dev), start, round_steps, 'philox', seed=seed,
                               offsets=torch.from_numpy(offs).to(dev), host=(order, offs, rng_rows), perm=perm,
-                              rng_rows=rng_dev, active=active)
+                              rng_rows=rng_dev, active=active, kept=kept)
     # explicit draws (tests replaying CPU noise; the emulation fallback): the reference's own loop
     # order, with the rows each head needs copied out of its full draw
     unmasked = torch.zeros(n, dtype=torch.uint8, device=dev)
+    if init is not None:
+        kept = _init_check(err, keep, T)  # (before the first draw)
+        unmasked.copy_(keep)  # kept rows start unmasked
     changes = torch.zeros(n, dtype=torch.uint8, device=dev)
     counts = torch.zeros(n_books + 1, dtype=torch.int32, device=dev)
     rows = torch.empty(n, dtype=torch.int32, device=dev)
@@ -626,10 +652,11 @@ def build_schedule(tex_tok, sample_steps, n_books, n_class, noise, compact=True,
             ops.gather_rows(e, torch.from_numpy(rh.astype(np.int32)).to(dev), len(rh), out=expo_rows[fill:fill + len(rh)])
             slot_of_row[rh] = np.arange(fill, fill + len(rh), dtype=np.int32)
             fill += len(rh)
-    assert fill == n, (fill, n)
-    order, start, round_steps = schedule.group_rounds(step_of_row, B, T, compact)
+    n_kept = int(kept.sum()) if kept is not None else 0
+    assert fill == n - n_kept, (fill, n, n_kept)
+    order, start, round_steps = schedule.group_rounds(step_of_row, B, T, compact, kept)
     return SampleSchedule(torch.from_numpy(order.astype(np.int32)).to(dev), start, round_steps, 'explicit',
-                          expo_rows=expo_rows, slots=torch.from_numpy(slot_of_row[order]).to(dev))
+                          expo_rows=expo_rows, slots=torch.from_numpy(slot_of_row[order]).to(dev), kept=kept)
 
 
 class RoundGraph:
@@ -647,7 +674,7 @@ class RoundGraph:
         # (a weak reference: net._graphs owns this object -- a strong one would make a cycle that only the cyclic
         # collector frees, at a moment of ITS choosing, e.g. in the middle of another graph's capture)
         self._net = weakref.ref(net)
-        self.maxr, self.temp, self.mask_id = maxr, float(temp), mask_id
+        self.maxr, self.temp, self.mask_id, self.n_class = maxr, float(temp), mask_id, n_class
         self.x_t, self.out, self.segm, self.tex = i64(B, T), i64(n_books, B * T), i64(B, T), i64(B, T)
         self.rows_tbl, self.offs_tbl, self.rng_tbl = i32(steps, maxr), i64(steps, maxr), i32(steps, maxr)
         self.cur_rows, self.cur_offs, self.cur_rng = i32(maxr), i64(maxr), i32(maxr)
@@ -702,9 +729,10 @@ class RoundGraph:
                 gc.enable()
         self.graphs[k] = g
 
-    def run(self, sched, segm_tok, tex_tok):
+    def run(self, sched, segm_tok, tex_tok, init=None):
         """All rounds of one run on this graph's stream; returns `out` (valid once the caller's stream
-        has waited, which this does)."""
+        has waited, which this does).  init = (src_lists, keep) in the schedule's sample order (region editing):
+        x_t / out start from t2h_edit_prefill instead of all-masked -- before the replays, outside any capture."""
         order, offs, rng_rows = sched.host
         tables = schedule.RoundTables(order, offs, sched.start, self.maxr, per_row32=rng_rows if rng_rows is not None else order)
         R, rows_tbl, offs_tbl = tables.n_rounds, tables.rows_tbl, tables.val_tbl
@@ -722,8 +750,12 @@ class RoundGraph:
             self.rng_tbl[:R].copy_(torch.from_numpy(tables.aux32_tbl), non_blocking=False)
             self.segm.copy_(segm_tok)
             self.tex.copy_(tex_tok)
-            self.x_t.fill_(self.mask_id)
-            self.out.fill_(-1)
+            if init is not None:
+                ops.edit_prefill(init[0], self.tex.view(-1), init[1], self.mask_id, self.n_class, x_t=self.x_t,
+                                 out=self.out)
+            else:
+                self.x_t.fill_(self.mask_id)
+                self.out.fill_(-1)
             self.round_ctr.zero_()
             self.seed.fill_(schedule.as_int64(sched.seed))  # (a uint64 seed >= 2^63 in its two's-complement form)
             for r in range(R):
@@ -735,7 +767,7 @@ class RoundGraph:
 
 
 def sample_tokens(net, segm_tok, tex_tok, sample_steps, mask_id, temp=1.0, noise=None,
-                  n_books=18, step_hook=None, round_hook=None, compact=None):
+                  n_books=18, step_hook=None, round_hook=None, compact=None, init=None):
     """BaseSampleModel.sample_fn (models/sample_model.py:256-328) on device.
 
     The unmasking schedule and every generator offset are computed up front (build_schedule: they
@@ -749,6 +781,10 @@ def sample_tokens(net, segm_tok, tex_tok, sample_steps, mask_id, temp=1.0, noise
     tests/test_gpu_edge_cases.py).
     compact=False: one round per step that changes a token, all samples at that step.
     Returns int64 [18, B*T] (-1 off-texture).
+
+    init = (src_lists int64 [n_books, B*T], keep uint8 [B*T]) -- region editing ("Editing a region"): the
+    rows with keep != 0 start as their source token and are never resampled; everything else is the loop above, with
+    the generator consumed exactly as the reference's loop started from that state would consume it.
 
     Test hooks, called after each round and allowed to overwrite x_t in place (teacher forcing):
     round_hook(r, steps, x_t, out) with steps[b] = the step sample b just took (0 = idle);
@@ -772,15 +808,23 @@ def sample_tokens(net, segm_tok, tex_tok, sample_steps, mask_id, temp=1.0, noise
     if split and getattr(net, 'x8', False):
         net.ensure_x8()  # (a no-op after the model's load-time calibration; bare SamplerNets of tests / tools)
         ops.split_overflow(reset=True)
-    sched = build_schedule(tex_tok, sample_steps, n_books, n_class, noise, compact, shrink)
+    if init is not None:
+        src_lists, keep = init
+        if tuple(src_lists.shape) != (n_books, n) or tuple(keep.shape) != (n, ):
+            raise ValueError(f'init: source lists [{n_books}, {n}] and keep [{n}] expected, got '
+                             f'{tuple(src_lists.shape)} / {tuple(keep.shape)}')
+    sched = build_schedule(tex_tok, sample_steps, n_books, n_class, noise, compact, shrink, init=init)
     defer = bool(split and getattr(net, 'split_mha', False) and os.environ.get('T2H_TRIM_LAST_LAYER', '1') != '0')
     # (only the deferred-tail form of hidden() runs on the prefix of running samples; every other form evaluates the
     # whole batch each round, and the counts say so)
-    net.last_stats = schedule.stats(sched.round_steps, sample_steps, sched.active if defer else None)
+    net.last_stats = schedule.stats(sched.round_steps, sample_steps, sched.active if defer else None, kept=sched.kept)
     if sched.perm is not None:
         perm_t = torch.from_numpy(sched.perm).to(dev)
         segm_tok, tex_tok = segm_tok[perm_t].contiguous(), tex_tok[perm_t].contiguous()
         tex_flat = tex_tok.reshape(-1)
+        if init is not None:  # the initial state in the schedule's sample order, like segm_tok / tex_tok
+            init = (src_lists.view(n_books, B, T)[:, perm_t].reshape(n_books, n).contiguous(),
+                    keep.view(B, T)[perm_t].reshape(n).contiguous())
 
     def in_batch_order(out):  # [n_books, n] in the schedule's sample order -> the caller's
         if sched.perm is None:
@@ -803,9 +847,14 @@ def sample_tokens(net, segm_tok, tex_tok, sample_steps, mask_id, temp=1.0, noise
         key = (B, T, sample_steps, maxr, float(temp), int(mask_id), n_books, bool(getattr(net, 'x8', False)))
         if key not in net._graphs:
             net._graphs[key] = RoundGraph(net, B, T, sample_steps, maxr, n_books, n_class, temp, mask_id, dev)
-        return in_batch_order(net._graphs[key].run(sched, segm_tok, tex_tok).clone())
-    x_t = torch.full((B, T), mask_id, dtype=torch.int64, device=dev)
-    out = torch.full((n_books, n), -1, dtype=torch.int64, device=dev)
+        return in_batch_order(net._graphs[key].run(sched, segm_tok, tex_tok, init=init).clone())
+    if init is not None:
+        x_t = torch.empty((B, T), dtype=torch.int64, device=dev)
+        out = torch.empty((n_books, n), dtype=torch.int64, device=dev)
+        ops.edit_prefill(init[0], tex_flat, init[1], mask_id, n_class, x_t=x_t, out=out)
+    else:
+        x_t = torch.full((B, T), mask_id, dtype=torch.int64, device=dev)
+        out = torch.full((n_books, n), -1, dtype=torch.int64, device=dev)
     logits_ws = torch.empty((max(sched.max_rows, 1), n_class), dtype=torch.float32, device=dev)
     for r in range(sched.n_rounds):
         lo, hi = int(sched.start[r]), int(sched.start[r + 1])

@@ -109,7 +109,10 @@ class BaseSampleModel():
     @torch.no_grad()
     def sample_fn(self, temp=1.0, sample_steps=None):
         """models/sample_model.py:256-328 -> list of 18 int64 [B, 512]."""
-        sample_steps = sample_steps or self.sample_steps
+        return self._sample(temp, sample_steps or self.sample_steps)
+
+    def _sample(self, temp, sample_steps, init=None):
+        """sample_fn's body (init: engine.sample_tokens' initial state of a region edit)."""
         tex_tok = self._texture_tokens(self.texture_mask)
         # The reference computes ANY checkpoint in fp32 (transformer_arch.py:91-99).  The split-precision kernels
         # cover |x| < 65504; an activation outside raises SplitOverflowError at the end of the run -- after
@@ -123,7 +126,7 @@ class BaseSampleModel():
             for _ in range(3):  # x8 planes -> fp16 planes -> exact fp32, each at most once
                 try:
                     out = engine.sample_tokens(net, self.segm_tokens.contiguous(), tex_tok, sample_steps, self.mask_id,
-                                               temp=temp, noise=self.noise)
+                                               temp=temp, noise=self.noise, init=init)
                     break
                 except engine.X8RangeError as e:
                     # an activation beyond 14x its calibration maximum: the 8-bit planes saturated, the fp16 planes are
@@ -142,6 +145,93 @@ class BaseSampleModel():
             self.sampler_fn.x8 = x8_was
         b = self.batch_size
         return [out[i].view(b, -1) for i in range(out.shape[0])]
+
+    # ------------------------------------------------------------ region editing
+    # DESIGN.md "Editing a region": the reference loop started from a partially known state.  A token row is kept
+    # (keep = 1) or resampled (keep = 0); kept rows start as their source token and are never drawn, everything else
+    # is sample_fn unchanged -- with keep all zero, resample_fn IS sample_fn (same tokens, same generator offset).
+    def _token_lists(self, lists, what):
+        """18 x [B, 512] (or [18, B*512]) int64 -> contiguous [18, B*512] on the device."""
+        n = self.batch_size * self.shape[0] * self.shape[1]
+        t = lists if torch.is_tensor(lists) else torch.stack([x.reshape(-1) for x in lists])
+        if t.numel() != 18 * n:
+            raise ValueError(f'{what}: 18 index lists of {n} tokens expected, got {tuple(t.shape)}')
+        return t.reshape(18, n).to(self.device, torch.int64).contiguous()
+
+    def _keep_rows(self, keep):
+        n_tok = self.shape[0] * self.shape[1]
+        if tuple(keep.shape) != (self.batch_size, n_tok):
+            raise ValueError(f'keep must be [{self.batch_size}, {n_tok}], got {tuple(keep.shape)}')
+        return keep.to(self.device, torch.uint8).reshape(-1).contiguous()
+
+    @torch.no_grad()
+    def region_keep(self, region=None, labels=None):
+        """-> uint8 [B, 512]: 1 for the token rows an edit keeps, 0 for the rows it resamples.  A row is resampled iff
+        ANY pixel of its H/32 x W/16 cell lies in the region: `region` [B, 1, H, W] (uint8 / bool / float, nonzero =
+        edit) or `labels` (parsing label ids, resolved against the current self.segm)."""
+        if (region is None) == (labels is None):
+            raise ValueError('region_keep: give exactly one of region (a pixel mask) or labels (parsing label ids)')
+        th, tw = self.shape
+        if region is not None:
+            b, hh, ww = self.batch_size, self.texture_mask.shape[2], self.texture_mask.shape[3]
+            if tuple(region.shape) != (b, 1, hh, ww):
+                raise ValueError(f'region must be [{b}, 1, {hh}, {ww}] like the texture map, got {tuple(region.shape)}')
+            m = region.to(self.device)
+            if m.dtype not in (torch.uint8, torch.bool, torch.float32):
+                m = m.to(torch.float32)
+            return ops.region_keep(b, hh, ww, (th, tw), mask=m.contiguous())
+        segm = self.segm.to(self.device, torch.float32).contiguous()  # (the dtype the tokenizer reads)
+        b, _, hh, ww = segm.shape
+        return ops.region_keep(b, hh, ww, (th, tw), parsing=segm, labels=[int(x) for x in labels])
+
+    @torch.no_grad()
+    def resample_fn(self, top_indices_list, keep, temp=1.0, sample_steps=None):
+        """sample_fn started from `top_indices_list` (18 x int64 [B, 512], e.g. an earlier sample_fn result or a photo's
+        top_encode indices) with the rows where keep [B, 512] is nonzero kept.  -> list of 18 int64 [B, 512] in
+        sample_fn's format.  A kept row must have an index under the CURRENT texture map (T2HError otherwise; nothing
+        changes)."""
+        init = (self._token_lists(top_indices_list, 'resample_fn'), self._keep_rows(keep))
+        return self._sample(temp, sample_steps or self.sample_steps, init=init)
+
+    @torch.no_grad()
+    def edit_and_refine(self, top_indices_list, region=None, labels=None, bot_indices_list=None, save_dir=None,
+                        img_name=None):
+        """Region edit end to end: resample the top tokens of the region (region_keep), predict the bottom indices,
+        keep `bot_indices_list` (e.g. a photo's bot_encode) outside the region if given, decode.  Return values and
+        files follow sample_and_refine: with save_dir and img_name both None the first image f32 [1, 3, H, W];
+        otherwise {save_dir}/{img_name[i]} PNGs are written and their uint8 [B, H, W, 3] pixels returned.  The edited
+        index lists are left in self.edit_top_indices_list / self.edit_bot_indices_list (18 x int64 [B, 512])."""
+        keep = self.region_keep(region, labels)
+        keep_rows = keep.reshape(-1).contiguous()
+        bot = None
+        if bot_indices_list is not None:
+            bot = self._token_lists(bot_indices_list, 'edit_and_refine (bot_indices_list)')
+            tex = self._texture_tokens(self.texture_mask).reshape(-1)
+            err = ops.edit_prefill(bot, tex, keep_rows, 0, self.P['bot.books'].shape[1])  # (check only)
+            engine._init_check(err, keep_rows, self.shape[0] * self.shape[1])
+        top = self.resample_fn(top_indices_list, keep)
+        want_files = not (save_dir is None and img_name is None)
+        bot_keep = (bot, keep_rows) if bot is not None else None
+        if not want_files:
+            keep_b, keep_mask = self.batch_size, self.texture_mask
+            t_len = self.shape[0] * self.shape[1]
+            self.batch_size, self.texture_mask = 1, self.texture_mask[:1]
+            try:
+                one = (bot[:, :t_len].contiguous(), keep_rows[:t_len]) if bot is not None else None
+                img, _, inter = self.decode_indices([t[:1] for t in top], return_inter=True, bot_keep=one)
+            finally:
+                self.batch_size, self.texture_mask = keep_b, keep_mask
+            self._edit_results(top, inter, 1)
+            return img
+        _, u8, inter = self.decode_indices(top, want_u8=True, return_inter=True, bot_keep=bot_keep)
+        self._edit_results(top, inter, self.batch_size)
+        save_u8_images(u8, save_dir, img_name)
+        return u8
+
+    def _edit_results(self, top, inter, b):
+        bot = torch.cat([d['bot_lists'] for d in inter], 1) if len(inter) > 1 else inter[0]['bot_lists']
+        self.edit_top_indices_list = top
+        self.edit_bot_indices_list = [bot[i].view(b, -1) for i in range(bot.shape[0])]
 
     def _exact_sampler(self):
         """The same transformer on the exact-fp32 matrix instructions (built on first use; shares the weights)."""
@@ -177,13 +267,16 @@ class BaseSampleModel():
         return [lists[i].view(b, self.shape[0], self.shape[1]) for i in range(lists.shape[0])]
 
     # ------------------------------------------------------------ stage D
-    def _decode(self, top_lists, tex_tok, b, want_u8=False, return_inter=False, upscale=False):
+    def _decode(self, top_lists, tex_tok, b, want_u8=False, return_inter=False, upscale=False, bot_keep=None):
         """sample_and_refine body after sample_fn (models/sample_model.py:220-246),
-        batched.  top_lists int64 [18, b*512]."""
+        batched.  top_lists int64 [18, b*512].  bot_keep = (bot_lists [18, b*512], keep uint8 [b*512]): the
+        predicted bottom indices are replaced by those where keep (region editing)."""
         P = self.P
         h, w = self.shape
         top_quant = self._top_quant_rows(top_lists, tex_tok)
         bot_lists = self._bot_indices(top_quant, tex_tok, b)
+        if bot_keep is not None:
+            ops.merge_kept_indices(bot_keep[0], bot_keep[1], bot_lists)
         quant_bot = ops.codebook_gather_fold(bot_lists, tex_tok.reshape(-1), P['bot.books'], b, h, w)
         quant_bot = ops.gemm(quant_bot, P['bot.pq.w'], bias=P['bot.pq.b'])
         bot_h = self.bot_decoder_res.decode_res(quant_bot, b, 2 * h, 2 * w, upscale=upscale)
@@ -194,13 +287,14 @@ class BaseSampleModel():
         return img, u8
 
     @torch.no_grad()
-    def decode_indices(self, top_indices_list, want_u8=False, return_inter=False, upscale=False):
+    def decode_indices(self, top_indices_list, want_u8=False, return_inter=False, upscale=False, bot_keep=None):
         """Batched refine + decode of sampled top indices (list of 18 [B,512]).
         upscale=True: 1024x512 output -- both quantised latents are nearest-x2
         upsampled before the (fully convolutional) decoders, the interpretation
-        of BASELINE.json configs[4] given in SURVEY.md 8(d)."""
+        of BASELINE.json configs[4] given in SURVEY.md 8(d).  bot_keep (region editing, edit_and_refine): see
+        _decode."""
         try:
-            return self._decode_indices(top_indices_list, want_u8, return_inter, upscale)
+            return self._decode_indices(top_indices_list, want_u8, return_inter, upscale, bot_keep)
         except engine.SplitOverflowError as e:
             # (decode draws no random numbers: simply once more, convolutions on the exact-fp32 kernels)
             if not _overflow_fallback('VQGAN refine / decode', 'T2H_SPLIT_CONV', e):
@@ -208,11 +302,11 @@ class BaseSampleModel():
             keep = self.decoder.use_split, self.bot_decoder_res.use_split
             self.decoder.use_split = self.bot_decoder_res.use_split = False
             try:
-                return self._decode_indices(top_indices_list, want_u8, return_inter, upscale)
+                return self._decode_indices(top_indices_list, want_u8, return_inter, upscale, bot_keep)
             finally:
                 self.decoder.use_split, self.bot_decoder_res.use_split = keep
 
-    def _decode_indices(self, top_indices_list, want_u8, return_inter, upscale):
+    def _decode_indices(self, top_indices_list, want_u8, return_inter, upscale, bot_keep=None):
         b = self.batch_size
         tex_tok = self._texture_tokens(self.texture_mask)
         top = torch.stack([t.reshape(-1) for t in top_indices_list]).contiguous()
@@ -221,8 +315,10 @@ class BaseSampleModel():
         chunk = max(1, DECODE_CHUNK // (4 if upscale else 1))
         for s in range(0, b, chunk):
             e = min(b, s + chunk)
+            bk = ((bot_keep[0][:, s * t_len:e * t_len].contiguous(), bot_keep[1][s * t_len:e * t_len])
+                  if bot_keep is not None else None)
             res = self._decode(top[:, s * t_len:e * t_len].contiguous(), tex_tok[s:e], e - s,
-                               want_u8=want_u8, return_inter=return_inter, upscale=upscale)
+                               want_u8=want_u8, return_inter=return_inter, upscale=upscale, bot_keep=bk)
             imgs.append(res[0])
             u8s.append(res[1])
             if return_inter:

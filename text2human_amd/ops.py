@@ -797,9 +797,10 @@ def philox_uniform(seed, offset, numel, device):
     return out
 
 
-def unmask_schedule(seed, offset, tex, steps, n_heads, n_class):
+def unmask_schedule(seed, offset, tex, steps, n_heads, n_class, keep=None):
     """The whole unmasking schedule of a sampling run on torch's device generator (seed, offset before
-    the first draw) in one launch (t2h_unmask_schedule).  tex int64 [n].  Returns
+    the first draw) in one launch (t2h_unmask_schedule).  tex int64 [n]; keep uint8 [n] (region editing,
+    t2h_unmask_schedule_keep): rows that start unmasked (step 0, never drawn).  Returns
     (step_of_row int32 [n], head_mask int32 [steps + 1], rand_inc, expo_inc) -- device tensors."""
     _chk_i64(tex)
     n = tex.numel()
@@ -808,10 +809,82 @@ def unmask_schedule(seed, offset, tex, steps, n_heads, n_class):
     _, expo_inc = torch_draw_geometry(n * n_class, dev)
     step_of_row = torch.empty(n, dtype=torch.int32, device=dev)
     head_mask = torch.empty(steps + 1, dtype=torch.int32, device=dev)
+    if keep is not None:
+        _chk_u8(keep, n)
+        check(_lib.load().t2h_unmask_schedule_keep(int(seed), int(offset), rand_gt, rand_inc, expo_inc, _p(tex),
+                                                   _p(keep), n, int(steps), int(n_heads), _p(step_of_row),
+                                                   _p(head_mask), _stream()), 't2h_unmask_schedule_keep')
+        return step_of_row, head_mask, rand_inc, expo_inc
     check(_lib.load().t2h_unmask_schedule(int(seed), int(offset), rand_gt, rand_inc, expo_inc, _p(tex), n, int(steps),
                                           int(n_heads), _p(step_of_row), _p(head_mask), _stream()),
           't2h_unmask_schedule')
     return step_of_row, head_mask, rand_inc, expo_inc
+
+
+def _chk_u8(t, n):
+    if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous() or t.numel() != n:
+        raise TypeError(f'expected a contiguous CUDA uint8 tensor of {n} elements, got {t.dtype} {tuple(t.shape)}')
+
+
+def edit_prefill(src_lists, tex, keep, mask_id, n_class, x_t=None, out=None, err=None):
+    """Initial state of a region edit (t2h_edit_prefill): src_lists int64 [n_heads, n], tex int64 [n], keep uint8 [n]
+    -> x_t [n] (kept rows: their source token, the rest mask_id) and out [n_heads, n] (the kept tokens, -1 elsewhere),
+    each written only if given.  err: uint32-sized int32 word [1] (zeroed here); after the launch it holds n - (first
+    kept row without a valid source token), 0 if there is none.  Returns err."""
+    _chk_i64(src_lists, tex)
+    n_heads, n = src_lists.shape
+    assert src_lists.is_contiguous() and tex.numel() == n
+    _chk_u8(keep, n)
+    if x_t is not None:
+        assert x_t.dtype == torch.int64 and x_t.is_contiguous() and x_t.numel() == n
+    if out is not None:
+        assert out.dtype == torch.int64 and out.is_contiguous() and tuple(out.shape) == (n_heads, n)
+    if err is None:
+        err = torch.empty(1, dtype=torch.int32, device=src_lists.device)
+    err.zero_()
+    check(_lib.load().t2h_edit_prefill(_p(src_lists), _p(tex), _p(keep), int(mask_id), _p(x_t), _p(out), _p(err), n,
+                                       n_heads, int(n_class), _stream()), 't2h_edit_prefill')
+    return err
+
+
+def region_keep(B, H, W, cells, mask=None, parsing=None, labels=None):
+    """Token rows an edit keeps (t2h_region_keep) -> uint8 [B, th * tw]: 0 iff any pixel of the row's cell is in the
+    region.  mask: uint8 / bool / fp32 [B, 1, H, W] (nonzero = region) or parsing: fp32 [B, 1, H, W] class ids with
+    labels: iterable of ids in [0, 64)."""
+    th, tw = cells
+    keep = torch.empty((B, th * tw), dtype=torch.uint8, device=(mask if mask is not None else parsing).device)
+    if mask is not None:
+        assert mask.is_contiguous() and mask.numel() == B * H * W
+        if mask.dtype in (torch.uint8, torch.bool):
+            mode, m8, mf = 0, mask.view(torch.uint8), None
+        elif mask.dtype == torch.float32:
+            mode, m8, mf = 1, None, mask
+        else:
+            raise TypeError(f'region mask must be uint8, bool or float32, got {mask.dtype}')
+        bits = 0
+    else:
+        _chk_f32(parsing)
+        assert parsing.is_contiguous() and parsing.numel() == B * H * W
+        mode, m8, mf = 2, None, parsing
+        bits = 0
+        for lb in labels:
+            if not 0 <= int(lb) < 64:
+                raise ValueError(f'label ids must lie in [0, 64), got {lb}')
+            bits |= 1 << int(lb)
+    check(_lib.load().t2h_region_keep(_p(m8), _p(mf), bits, mode, B, H, W, th, tw, _p(keep), _stream()),
+          't2h_region_keep')
+    return keep
+
+
+def merge_kept_indices(src_lists, keep, dst_lists):
+    """dst_lists[:, r] = src_lists[:, r] where keep[r] (t2h_merge_kept_indices, in place; [n_heads, n] int64)."""
+    _chk_i64(src_lists, dst_lists)
+    n_heads, n = dst_lists.shape
+    assert src_lists.is_contiguous() and dst_lists.is_contiguous() and tuple(src_lists.shape) == (n_heads, n)
+    _chk_u8(keep, n)
+    check(_lib.load().t2h_merge_kept_indices(_p(src_lists), _p(keep), _p(dst_lists), n, n_heads, _stream()),
+          't2h_merge_kept_indices')
+    return dst_lists
 
 
 def schedule_advance(rows_tbl, aux64_tbl, aux32_tbl, round_ctr, cur_rows, cur_aux64, cur_aux32, maxr):

@@ -51,50 +51,70 @@ def draw_offsets(head_mask, steps, offset0, rand_inc, expo_inc, n_heads):
     return rand_off, expo_off, cur
 
 
-def group_rounds(step_of_row, B, T, compact=True):
+def _kept_mask(step_of_row, kept):
+    """(steps int64 [B*T], kept bool [B*T]).  Without `kept` every row needs a step >= 1; with it (region editing: the
+    rows that keep their source token) exactly the kept rows have step 0."""
+    steps = np.asarray(step_of_row, dtype=np.int64).reshape(-1)
+    if kept is None:
+        if steps.size and steps.min() < 1:
+            raise ValueError('every token row must have a step >= 1')
+        return steps, np.zeros(steps.size, dtype=bool)
+    kept = np.asarray(kept).reshape(-1).astype(bool)
+    if kept.size != steps.size:
+        raise ValueError(f'kept has {kept.size} rows, the schedule {steps.size}')
+    if (steps[~kept] < 1).any() or (steps[kept] != 0).any():
+        raise ValueError('every token row that is not kept must have a step >= 1, every kept row step 0')
+    return steps, kept
+
+
+def group_rounds(step_of_row, B, T, compact=True, kept=None):
     """Rounds of the sampling loop.
 
     step_of_row int [B*T]: the step (>= 1) at which each token row changes.  compact=True: round r
     of sample b is its r-th active step (descending t); compact=False: round r is the r-th step (of
     any sample) that changes a token, for every sample alike -- the reference's own loop minus the
-    steps that change nothing.  Returns
-      order        int64 [B*T]   row ids sorted by (round, row),
+    steps that change nothing.  kept bool [B*T] (region editing): rows that keep their source token
+    (step 0); they take part in no round, and `order` lists only the other rows.  Returns
+      order        int64 [B*T]   row ids sorted by (round, row) (without the kept rows),
       start        int64 [R + 1] order[start[r]:start[r + 1]] are the rows of round r,
       round_steps  int32 [R, B]  the step sample b is at in round r (0 = idle in that round)."""
-    steps = np.asarray(step_of_row, dtype=np.int64).reshape(B, T)
-    if steps.min() < 1:
-        raise ValueError('every token row must have a step >= 1')
+    flat_steps, kept_flat = _kept_mask(step_of_row, kept)
+    steps = flat_steps.reshape(B, T)
+    live = ~kept_flat.reshape(B, T)
     if compact:
-        uniq = [np.unique(steps[b]) for b in range(B)]            # ascending
+        uniq = [np.unique(steps[b][live[b]]) for b in range(B)]   # ascending
     else:
-        g = np.unique(steps)
+        g = np.unique(steps[live])
         uniq = [g] * B
-    n_rounds = max(len(u) for u in uniq)
-    rnd = np.empty((B, T), dtype=np.int64)
+    n_rounds = max([len(u) for u in uniq] + [0])
+    rnd = np.full((B, T), n_rounds, dtype=np.int64)                # kept rows: after the last round
     round_steps = np.zeros((n_rounds, B), dtype=np.int32)
     for b in range(B):
         u = uniq[b]
-        rnd[b] = len(u) - 1 - np.searchsorted(u, steps[b])       # descending t = ascending round
+        rnd[b][live[b]] = len(u) - 1 - np.searchsorted(u, steps[b][live[b]])   # descending t = ascending round
         if compact:
             round_steps[:len(u), b] = u[::-1]
         else:
-            present = np.isin(u, steps[b])
+            present = np.isin(u, steps[b][live[b]])
             round_steps[:len(u), b] = np.where(present, u, 0)[::-1]
     flat = rnd.reshape(-1)
     order = np.lexsort((np.arange(B * T), flat)).astype(np.int64)
     start = np.searchsorted(flat[order], np.arange(n_rounds + 1)).astype(np.int64)
+    if kept is not None:
+        order = order[:start[-1]]
     return order, start, round_steps
 
 
-def leave_order(step_of_row, B, T):
+def leave_order(step_of_row, B, T, kept=None):
     """Order of the samples for a compact schedule in which FINISHED samples leave the batch: samples sorted by the
     number of rounds they take part in (= their distinct steps), descending, ties in index order.  With the batch in
     this order the samples still active in round r are exactly the first k_r, so the transformer of round r runs on
     the first k_r * T rows only (about 2 % of the evaluations at B = 8, 3.5 % at B = 32, are (sample, round) pairs of
-    samples that have no step left).  -> (perm int64 [B]: new position -> original sample, rounds per sample in the
-    new order)"""
-    steps = np.asarray(step_of_row, dtype=np.int64).reshape(B, T)
-    n_act = np.array([len(np.unique(steps[b])) for b in range(B)], dtype=np.int64)
+    samples that have no step left).  kept (region editing): kept rows count for no round -- a fully kept sample has
+    none and sorts last.  -> (perm int64 [B]: new position -> original sample, rounds per sample in the new order)"""
+    flat_steps, kept_flat = _kept_mask(step_of_row, kept)
+    steps, live = flat_steps.reshape(B, T), ~kept_flat.reshape(B, T)
+    n_act = np.array([len(np.unique(steps[b][live[b]])) for b in range(B)], dtype=np.int64)
     perm = np.argsort(-n_act, kind='stable').astype(np.int64)
     return perm, n_act[perm]
 
@@ -148,13 +168,17 @@ class RoundTables:
         return self.n_rounds - (1 if first_eager and self.n_rounds else 0)
 
 
-def stats(round_steps, steps, active=None):
+def stats(round_steps, steps, active=None, kept=None):
     """Evaluation counts for the bench line: (sample, step) pairs the reference evaluates, pairs that
     change a token (the ones whose logits are read), rounds launched, and the (sample, round) pairs the
-    transformer was actually run for (`active[r]` samples in round r; default: the whole batch)."""
+    transformer was actually run for (`active[r]` samples in round r; default: the whole batch).  With
+    `kept` (region editing) also the number of kept rows."""
     n_rounds, B = round_steps.shape
     launched = int(n_rounds * B) if active is None else int(np.asarray(active).sum())
-    return dict(rounds=int(n_rounds), steps=int(steps), batch=int(B),
-                sample_steps_possible=int(B * steps),
-                sample_steps_needed=int((round_steps > 0).sum()),
-                sample_steps_launched=launched)
+    out = dict(rounds=int(n_rounds), steps=int(steps), batch=int(B),
+               sample_steps_possible=int(B * steps),
+               sample_steps_needed=int((round_steps > 0).sum()),
+               sample_steps_launched=launched)
+    if kept is not None:
+        out['rows_kept'] = int(np.asarray(kept).astype(bool).sum())
+    return out
