@@ -99,14 +99,15 @@ def build(kernel_file, transform=None, tag=''):
     return lib
 
 
-def load(kernel_file):
-    """-> ctypes handle of the emulation library of csrc/<kernel_file>, every product entry point it exports typed
-    from text2human_amd._lib.SIGNATURES (the table the product's own loader uses)"""
+def load(kernel_file, **build_kw):
+    """-> ctypes handle of the emulation library of csrc/<kernel_file> (build_kw: build's transform / tag), every
+    product entry point it exports typed from text2human_amd._lib.SIGNATURES (the table the product's own loader
+    uses, pinned to include/t2h_hip.h by tests/test_cabi.py); the emu_* symbols are the caller's to declare"""
     import ctypes
     import sys
     sys.path.insert(0, ROOT)
     from text2human_amd import _lib
-    so = ctypes.CDLL(build(kernel_file))
+    so = ctypes.CDLL(build(kernel_file, **build_kw))
     for name, (res, args) in _lib.SIGNATURES.items():
         try:
             fn = getattr(so, name)

@@ -26,12 +26,9 @@ pytestmark = pytest.mark.skipif(not build_emu.available(), reason='no host clang
 @pytest.fixture(scope='module', params=[(1, 0), (1, 1), (0, 1)],
                 ids=['lds-dma-kernel', 'lds-dma-kernel-late-landing', 'first-version-late-landing'])
 def lib(request):
-    so = ctypes.CDLL(build_emu.build('conv_halo.hip'))
+    so = build_emu.load('conv_halo.hip')
     so.t2h_conv_halo_force_variant(request.param[0])
     so.emu_set_deferred(request.param[1])
-    so.t2h_conv_halo_f32.restype = ctypes.c_int
-    so.t2h_conv_halo_f32.argtypes = [ctypes.POINTER(GemmArgs), ctypes.c_void_p, ctypes.c_void_p]
-    so.emu_last_error.restype = ctypes.c_char_p
     return so
 
 
@@ -145,10 +142,7 @@ def test_late_landing_catches_a_wait_count_that_is_one_too_permissive():
         old = 'ch_wait_vm_all<(t >= 1 && t <= 6) ? 3 : 2>();'
         assert old in text
         return text.replace(old, 'ch_wait_vm_all<(t >= 1 && t <= 6) ? 4 : 3>();')
-    so = ctypes.CDLL(build_emu.build('conv_halo.hip', transform=relax, tag='_relaxed_wait'))
-    so.t2h_conv_halo_f32.restype = ctypes.c_int
-    so.t2h_conv_halo_f32.argtypes = [ctypes.POINTER(GemmArgs), ctypes.c_void_p, ctypes.c_void_p]
-    so.emu_last_error.restype = ctypes.c_char_p
+    so = build_emu.load('conv_halo.hip', transform=relax, tag='_relaxed_wait')
     so.emu_set_deferred(0)
     out, ref, _, _, _ = run(so, 1, 64, 128, 16, 16, 'same', True)
     assert ((out.double() - ref).abs() <= 2e-5 + 2e-5 * ref.abs()).all()   # landing at issue: the count is never tested

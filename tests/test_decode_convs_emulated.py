@@ -18,29 +18,16 @@ from text2human_amd import ops, weights  # noqa: E402
 from text2human_amd._lib import GemmArgs  # noqa: E402
 
 pytestmark = pytest.mark.skipif(not build_emu.available(), reason='no host clang++ for the emulation build')
-c_vp, c_i32, c_i64, c_f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
-
-
-def _load(kernel_file, sigs):
-    so = ctypes.CDLL(build_emu.build(kernel_file))
-    for name, args in sigs.items():
-        getattr(so, name).restype = ctypes.c_int
-        getattr(so, name).argtypes = args
-    so.emu_last_error.restype = ctypes.c_char_p
-    return so
 
 
 @pytest.fixture(scope='module')
 def norm():
-    return _load('norm.hip', {
-        't2h_gn_apply_split_f32': [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp],
-        't2h_groupnorm_finalize_f32': [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp]})
+    return build_emu.load('norm.hip')
 
 
 @pytest.fixture(scope='module', params=[0, 1], ids=['requests-land-at-issue', 'requests-land-at-the-wait'])
 def conv_split(request):
-    so = _load('conv_split.hip', {'t2h_conv_split_f32': [ctypes.POINTER(GemmArgs), c_vp],
-                                  't2h_conv_split_force_tile': [ctypes.c_int]})
+    so = build_emu.load('conv_split.hip')
     so.emu_set_deferred(request.param)   # (its staged pieces are explicit requests with exact vmcnt waits)
     yield so
     so.emu_set_deferred(0)
@@ -48,7 +35,7 @@ def conv_split(request):
 
 @pytest.fixture(scope='module')
 def conv_halo():
-    return _load('conv_halo.hip', {'t2h_conv_halo_f32': [ctypes.POINTER(GemmArgs), c_vp, c_vp]})
+    return build_emu.load('conv_halo.hip')
 
 
 def rnd(*shape, seed=0, scale=1.0):
@@ -174,8 +161,7 @@ def test_emulated_conv_split_vs_fp64_and_vs_the_halo_kernel(norm, conv_split, co
 def test_emulated_layernorm_with_its_dpp_reduction(C):
     """csrc/norm.hip's LayerNorm (one row per wave, the two reductions by DPP + v_readlane: tests/emu/hip_emu.h restates
     the four DPP controls as lane exchanges) against torch, fp32 out and split rows out."""
-    so = _load('norm.hip', {'t2h_layernorm_f32': [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_vp],
-                            't2h_layernorm_split_f32': [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_vp, c_vp]})
+    so = build_emu.load('norm.hip')
     rows = 11   # (a partly filled second workgroup)
     x = rnd(rows, C, seed=21) * 2.0 + 0.3
     g, b = rnd(C, seed=22) * 0.2 + 1.0, rnd(C, seed=23) * 0.1

@@ -17,21 +17,11 @@ from text2human_amd import weights  # noqa: E402
 from text2human_amd._lib import GemmArgs  # noqa: E402
 
 pytestmark = pytest.mark.skipif(not build_emu.available(), reason='no host clang++ for the emulation build')
-c_vp, c_i32, c_f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float
-
-
-def _load(kernel_file, sigs):
-    so = ctypes.CDLL(build_emu.build(kernel_file))
-    for name, args in sigs.items():
-        getattr(so, name).restype = ctypes.c_int
-        getattr(so, name).argtypes = args
-    so.emu_last_error.restype = ctypes.c_char_p
-    return so
 
 
 @pytest.fixture(scope='module', params=[0, 1], ids=['requests-land-at-issue', 'requests-land-at-the-wait'])
 def gemm(request):
-    so = _load('gemm.hip', {'t2h_gemm_f32': [ctypes.POINTER(GemmArgs), c_vp], 't2h_gemm_force_config': [ctypes.c_int]})
+    so = build_emu.load('gemm.hip')
     so.emu_set_deferred(request.param)   # (register pieces in flight across two K tiles, counted waits)
     yield so
     so.emu_set_deferred(0)
@@ -116,8 +106,6 @@ def test_emulated_conv_split_over_k_for_the_deep_unet_levels(gemm):
     slices on their own workgroups, partial tiles in the caller's workspace, summed in slice order with bias / ReLU /
     residual behind.  The automatic slice count depends on (K, N, pixels per image) only: one image computed alone
     and inside a batch gives the same bits."""
-    gemm.t2h_gemm_ksplit.restype = ctypes.c_int
-    gemm.t2h_gemm_ksplit.argtypes = [ctypes.POINTER(GemmArgs)]
     n_img, cin, cout, h, w = 2, 32, 40, 4, 2
     x = rnd(n_img, cin, h, w, seed=31)
     wt, b = rnd(cout, cin, 3, 3, seed=32, scale=0.1), rnd(cout, seed=33)
@@ -154,8 +142,7 @@ def test_emulated_conv_split_over_k_for_the_deep_unet_levels(gemm):
 
 
 def test_emulated_conv_out_on_the_vector_alu():
-    so = _load('conv_small.hip', {'t2h_conv3x3_small_f32': [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32,
-                                                            c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]})
+    so = build_emu.load('conv_small.hip')
     n_img, cin, cout, h, w = 2, 32, 3, 12, 20
     x = rnd(n_img, cin, h, w, seed=13)
     wt, b = rnd(cout, cin, 3, 3, seed=14, scale=0.1), rnd(cout, seed=15)
@@ -172,7 +159,7 @@ def test_emulated_conv_out_on_the_vector_alu():
 
 
 def test_emulated_flash_style_spatial_attention():
-    so = _load('spatial_attn.hip', {'t2h_spatial_attention_f32': [c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp]})
+    so = build_emu.load('spatial_attn.hip')
     n_img, N, C = 2, 96, 256
     qkv = rnd(n_img * N, 3 * C, seed=18) * 0.5
     out = torch.full((n_img * N, C), float('nan'))

@@ -17,19 +17,11 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'emu
 import build_emu  # noqa: E402
 
 pytestmark = pytest.mark.skipif(not build_emu.available(), reason='no host clang++ for the emulation build')
-c_vp, c_i32, c_i64, c_u32, c_u64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_uint64
 
 
 @pytest.fixture(scope='module')
 def lib():
-    so = ctypes.CDLL(build_emu.build('sampler.hip'))
-    for name, args in {'t2h_philox_uniform_f32': [c_u64, c_u64, c_u32, c_vp, c_i64, c_vp],
-                       't2h_philox_exponential_f32': [c_u64, c_u64, c_u32, c_vp, c_i64, c_vp],
-                       't2h_unmask_schedule': [c_u64, c_u64, c_u32, c_u32, c_u32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]}.items():
-        getattr(so, name).restype = ctypes.c_int
-        getattr(so, name).argtypes = args
-    so.emu_last_error.restype = ctypes.c_char_p
-    return so
+    return build_emu.load('sampler.hip')
 
 
 def philox4x32_10(counter, key):
@@ -130,10 +122,7 @@ def test_emulated_sampling_tail_is_the_exponential_race_of_the_reference():
     two-launch form drawing the noise itself (element (row, class) of the tensor torch would have drawn at the head's
     generator offset) -- against fp64 on the same noise."""
     from text2human_amd._lib import SampleHeadsArgs
-    so = ctypes.CDLL(build_emu.build('sampler.hip'))
-    so.t2h_sample_heads.restype = ctypes.c_int
-    so.t2h_sample_heads.argtypes = [ctypes.POINTER(SampleHeadsArgs), c_vp]
-    so.emu_last_error.restype = ctypes.c_char_p
+    so = build_emu.load('sampler.hip')
     n, C, n_class, n_heads, temp = 24, 512, 128, 4, 0.9
     g = torch.Generator().manual_seed(12)
     hidden = torch.randn(n, C, generator=g) * 1.5 + 0.2

@@ -3,7 +3,6 @@ product entry point): the segm tokenizer's codebook argmin (T-3, vqgan_arch.py:8
 texture-routed argmin of the encode side, the texture-routed codebook gather (R-1), the image epilogue (D-5,
 sample_model.py:245-254: the uint8 rounding bit for bit) and the texture map (P-3).  Decisions are compared with fp64
 where the margin to the runner-up is not a rounding matter, exactly otherwise."""
-import ctypes
 import os
 import sys
 
@@ -14,30 +13,16 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'emu
 import build_emu  # noqa: E402
 
 pytestmark = pytest.mark.skipif(not build_emu.available(), reason='no host clang++ for the emulation build')
-c_vp, c_i32, c_i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-
-
-def _load(kernel_file, sigs):
-    so = ctypes.CDLL(build_emu.build(kernel_file))
-    for name, args in sigs.items():
-        getattr(so, name).restype = ctypes.c_int
-        getattr(so, name).argtypes = args
-    so.emu_last_error.restype = ctypes.c_char_p
-    return so
 
 
 @pytest.fixture(scope='module')
 def vq():
-    return _load('vq.hip', {
-        't2h_vq_l2_argmin_f32': [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp],
-        't2h_vq_argmin_tex_f32': [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp],
-        't2h_codebook_gather_tex_f32': [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]})
+    return build_emu.load('vq.hip')
 
 
 @pytest.fixture(scope='module')
 def misc():
-    return _load('misc.hip', {'t2h_image_epilogue': [c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp],
-                              't2h_texture_map': [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]})
+    return build_emu.load('misc.hip')
 
 
 def rnd(*shape, seed=0, scale=1.0):

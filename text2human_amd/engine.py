@@ -179,6 +179,86 @@ class VQGANStack:
 # ---------------------------------------------------------------- transformer
 
 
+class _ExactFp32:
+    """One arithmetic of the sampler's layer (SamplerNet._attention_half / _tail_half spell the layer itself): which
+    buffers of SamplerNet._buffers hold the operands and how the norm producer, a Linear and attention are called.
+    This one: fp32 operands, the exact-fp32 kernels."""
+
+    def __init__(self, net, mha=True):
+        self.P, self.nm, self.n_head, self.mha = net.P, net.name, net.n_head, mha
+
+    def buffers(self, buf):
+        """(h, qk, vt, y, u): LayerNorm output, q|k|v, transposed values, attention output, GELU output"""
+        return buf['h'], buf['qkv'], None, buf['y'], buf['u']
+
+    def norm(self, i, ln, x, out, role):
+        p = f'{self.nm}.{i}.{ln}'
+        ops.layernorm(x, self.P[f'{p}.g'], self.P[f'{p}.b'], out=out)
+
+    def linear(self, i, lin, a, role, m, N, K, dst, to=None, residual=None, act=ACT_NONE):
+        """dst[:m] = act(a @ W(i, lin)^T + b) + residual.  role: what `a` is (h1 / y / h2 / u); to: what dst is if it
+        is an operand of the next kernel (u, qk), None: fp32 rows."""
+        p = f'{self.nm}.{i}.{lin}'
+        ops.gemm(a, self.P[f'{p}.w'], out=dst, bias=self.P[f'{p}.b'], residual=residual, act=act)
+
+    def qkv(self, i, h, m, C, qk, vt, T):
+        self.linear(i, 'qkv', h, 'h1', m, 3 * C, C, qk)
+
+    def attention(self, i, qk, vt, B, T, C, y):
+        ops.mha_noncausal(qk, B, T, self.n_head, out=y)
+
+
+class _Fp16Planes(_ExactFp32):
+    """Split precision: the four Linears run on the fp16 matrix cores with 2 x fp16 planes per operand (fp32-class
+    accuracy, gemm_split.hip).  The producers write split rows directly: LayerNorm -> h, attention -> y, fc1's GELU
+    epilogue -> u; the residual stream x stays fp32.  mha (split_mha): attention on the fp16 matrix cores too -- the
+    q|k|v projection writes q, k as split rows and v as transposed planes; without it an fp32 qkv."""
+    key = 'w_split'
+
+    def buffers(self, buf):
+        return buf['h_split'], buf['qk_split'] if self.mha else buf['qkv'], buf['vt'], buf['y_split'], buf['u_split']
+
+    def norm(self, i, ln, x, out, role):
+        p = f'{self.nm}.{i}.{ln}'
+        ops.layernorm_split(x, self.P[f'{p}.g'], self.P[f'{p}.b'], out)
+
+    def linear(self, i, lin, a, role, m, N, K, dst, to=None, residual=None, act=ACT_NONE, **fmt):
+        p = f'{self.nm}.{i}.{lin}'
+        ops.gemm_split(a, self.P[f'{p}.{self.key}'], m, N, K, out=None if to else dst, out_split=dst if to else None,
+                       bias=self.P[f'{p}.b'], residual=residual, act=act, **fmt)
+
+    def qkv(self, i, h, m, C, qk, vt, T):
+        if not self.mha:
+            return self.linear(i, 'qkv', h, 'h1', m, 3 * C, C, qk)
+        self.linear(i, 'qkv', h, 'h1', m, 3 * C, C, qk, to='qk', vt=vt, vt_col0=2 * C, vt_T=T, vt_hd=C // self.n_head)
+
+    def attention(self, i, qk, vt, B, T, C, y):
+        if not self.mha:
+            return ops.mha_noncausal_split(qk, B, T, self.n_head, y)
+        ops.mha_split(qk, 3 * C, vt, B, T, self.n_head, out_split=y)
+
+
+class _X8(_Fp16Planes):
+    """x8 operands (fp16 plane + two e4m3 planes, csrc/common.h), each with the calibrated power-of-two scale of its
+    (layer, role) -- activations -- or (layer, Linear) -- weights (SamplerNet.calibrate_x8)."""
+    key = 'w_x8'
+
+    def __init__(self, net):
+        super().__init__(net)
+        self.sw, self.sa = net._x8['w'], net._x8['a']
+
+    def norm(self, i, ln, x, out, role):
+        p = f'{self.nm}.{i}.{ln}'
+        ops.layernorm_x8(x, self.P[f'{p}.g'], self.P[f'{p}.b'], out, self.sa[i, role])
+
+    def linear(self, i, lin, a, role, *args, to=None, **kw):
+        super().linear(i, lin, a, role, *args, to=to, x8=(self.sa[i, role], self.sw[i, lin]),
+                       out_x8_scale=self.sa.get((i, to)), **kw)
+
+    def attention(self, i, qk, vt, B, T, C, y):
+        ops.mha_split_x8(qk, 3 * C, vt, B, T, self.n_head, y, self.sa[i, 'y'])
+
+
 class SamplerNet:
     """TransformerMultiHead.forward (models/archs/transformer_arch.py:249-273)
     up to (not including) ln_f; ln_f + the routed head live in the sampling
@@ -233,6 +313,38 @@ class SamplerNet:
     # (tests/test_gpu_edge_cases.py compares the tokens of both forms on the bench configuration).
     TRIM_MAX_ROWS = 256
 
+    def _arithmetic(self):
+        """The arithmetic of this call (looked up per call: a caller may switch `x8` off for one run)."""
+        if not self.split:
+            return _ExactFp32(self)
+        if self.x8 and self.split_mha:
+            # (bare SamplerNets of tests / tools; the models calibrate when the checkpoint is packed.  It runs in
+            # buffers of its own and may switch x8 off for a checkpoint that leaves fp16's range)
+            if self.ensure_x8().x8:
+                return _X8(self)
+        return _Fp16Planes(self, self.split_mha)
+
+    def _attention_half(self, ar, i, B, T, x, h, qk, vt, y, observe=None):
+        """Layer i, first half: LN1 -> q|k|v Linear -> attention, on the arithmetic `ar` and its buffers (ar.buffers);
+        observe(layer, role, tensor, rows, cols) sees every producer's output (calibrate_x8)."""
+        M, C = B * T, self.desc['C']
+        ar.norm(i, 'ln1', x, h, 'h1')
+        observe and observe(i, 'h1', h, M, C)
+        ar.qkv(i, h, M, C, qk, vt, T)
+        ar.attention(i, qk, vt, B, T, C, y)
+        observe and observe(i, 'y', y, M, C)
+
+    def _tail_half(self, ar, i, m, x, y, h, u, observe=None):
+        """proj + residual -> LN2 -> fc1 + GELU -> fc2 + residual on the first m rows of x (row-wise: the whole
+        batch, or finish_tail's compacted rows)."""
+        C = self.desc['C']
+        ar.linear(i, 'proj', y, 'y', m, C, C, x, residual=x)
+        ar.norm(i, 'ln2', x, h, 'h2')
+        observe and observe(i, 'h2', h, m, C)
+        ar.linear(i, 'fc1', h, 'h2', m, 4 * C, C, u, to='u', act=ACT_GELU)
+        observe and observe(i, 'u', u, m, 4 * C)
+        ar.linear(i, 'fc2', u, 'u', m, C, 4 * C, x, residual=x)
+
     def hidden(self, idx, segm_tok, tex_tok, defer_tail=False, active=None):
         """active = k < B: only the first k samples of the batch, on the first k * T rows of the SAME buffers
         (samples never interact: attention is per sample) -- the samples of a compact schedule that have no step
@@ -249,73 +361,21 @@ class SamplerNet:
             buf = {name: (v[:k] if name == 'vt' else v[:k * T]) for name, v in full.items()
                    if name not in ('xc', 'yc', 'hc', 'uc')}
             idx, segm_tok, tex_tok, B = idx[:k], segm_tok[:k], tex_tok[:k], k
-        x, h, qkv, y, u = buf['x'], buf['h'], buf['qkv'], buf['y'], buf['u']
+        x = buf['x']
         ops.embed_sum4(idx, segm_tok, tex_tok, P[f'{nm}.tok_emb'], P[f'{nm}.pos_emb'],
                        P[f'{nm}.segm_emb'], P[f'{nm}.tex_emb'], out=x)
         L = self.desc['n_layers']
         self._deferred = None
-        if self.split:
-            # Split-precision path: the four Linears run on the fp16 matrix cores with
-            # 2 x fp16 planes per operand (fp32-class accuracy, gemm_split.hip).  The
-            # producers write split rows directly: LayerNorm -> h, attention -> y,
-            # fc1's GELU epilogue -> u; the residual stream x stays fp32.
-            M = B * T
-            hs, ys, us, qks = buf['h_split'], buf['y_split'], buf['u_split'], buf['qk_split']
-            vt = buf['vt']
-            hd = C // self.n_head
-            if self.x8 and self.split_mha and self._x8 is None:
-                # (bare SamplerNets of tests / tools; the models calibrate when the checkpoint is packed.  It runs in
-                # buffers of its own and may switch x8 off for a checkpoint that leaves fp16's range)
-                self.ensure_x8()
-            if self.x8 and self.split_mha:
-                sw, sa = self._x8['w'], self._x8['a']
-                for i in range(L):
-                    p = f'{nm}.{i}'
-                    ops.layernorm_x8(x, P[f'{p}.ln1.g'], P[f'{p}.ln1.b'], hs, sa[i, 'h1'])
-                    ops.gemm_split(hs, P[f'{p}.qkv.w_x8'], M, 3 * C, C, out_split=qks, bias=P[f'{p}.qkv.b'],
-                                   vt=vt, vt_col0=2 * C, vt_T=T, vt_hd=hd, x8=(sa[i, 'h1'], sw[i, 'qkv']))
-                    ops.mha_split_x8(qks, 3 * C, vt, B, T, self.n_head, ys, sa[i, 'y'])
-                    if i == L - 1 and defer_tail:
-                        self._deferred = (full['x'], full['y_split'], M, C)
-                        return x
-                    ops.gemm_split(ys, P[f'{p}.proj.w_x8'], M, C, C, out=x, bias=P[f'{p}.proj.b'], residual=x,
-                                   x8=(sa[i, 'y'], sw[i, 'proj']))
-                    ops.layernorm_x8(x, P[f'{p}.ln2.g'], P[f'{p}.ln2.b'], hs, sa[i, 'h2'])
-                    ops.gemm_split(hs, P[f'{p}.fc1.w_x8'], M, 4 * C, C, out_split=us, bias=P[f'{p}.fc1.b'],
-                                   act=ACT_GELU, x8=(sa[i, 'h2'], sw[i, 'fc1']), out_x8_scale=sa[i, 'u'])
-                    ops.gemm_split(us, P[f'{p}.fc2.w_x8'], M, C, 4 * C, out=x, bias=P[f'{p}.fc2.b'], residual=x,
-                                   x8=(sa[i, 'u'], sw[i, 'fc2']))
-                return x
-            for i in range(L):
-                p = f'{nm}.{i}'
-                ops.layernorm_split(x, P[f'{p}.ln1.g'], P[f'{p}.ln1.b'], hs)
-                if self.split_mha:
-                    ops.gemm_split(hs, P[f'{p}.qkv.w_split'], M, 3 * C, C, out_split=qks, bias=P[f'{p}.qkv.b'],
-                                   vt=vt, vt_col0=2 * C, vt_T=T, vt_hd=hd)
-                    ops.mha_split(qks, 3 * C, vt, B, T, self.n_head, out_split=ys)
-                else:
-                    ops.gemm_split(hs, P[f'{p}.qkv.w_split'], M, 3 * C, C, out=qkv, bias=P[f'{p}.qkv.b'])
-                    ops.mha_noncausal_split(qkv, B, T, self.n_head, ys)
-                if i == L - 1 and defer_tail:
-                    # (the WHOLE batch's buffers: finish_tail addresses rows by their index in the batch; only
-                    # the first M rows -- the active samples -- were evaluated, and only they are listed)
-                    self._deferred = (full['x'], full['y_split'], M, C)
-                    return x
-                ops.gemm_split(ys, P[f'{p}.proj.w_split'], M, C, C, out=x, bias=P[f'{p}.proj.b'], residual=x)
-                ops.layernorm_split(x, P[f'{p}.ln2.g'], P[f'{p}.ln2.b'], hs)
-                ops.gemm_split(hs, P[f'{p}.fc1.w_split'], M, 4 * C, C, out_split=us, bias=P[f'{p}.fc1.b'],
-                               act=ACT_GELU)
-                ops.gemm_split(us, P[f'{p}.fc2.w_split'], M, C, 4 * C, out=x, bias=P[f'{p}.fc2.b'], residual=x)
-            return x
+        ar = self._arithmetic()
+        h, qk, vt, y, u = ar.buffers(buf)
         for i in range(L):
-            p = f'{nm}.{i}'
-            ops.layernorm(x, P[f'{p}.ln1.g'], P[f'{p}.ln1.b'], out=h)
-            ops.gemm(h, P[f'{p}.qkv.w'], out=qkv, bias=P[f'{p}.qkv.b'])
-            ops.mha_noncausal(qkv, B, T, self.n_head, out=y)
-            ops.gemm(y, P[f'{p}.proj.w'], out=x, bias=P[f'{p}.proj.b'], residual=x)
-            ops.layernorm(x, P[f'{p}.ln2.g'], P[f'{p}.ln2.b'], out=h)
-            ops.gemm(h, P[f'{p}.fc1.w'], out=u, bias=P[f'{p}.fc1.b'], act=ACT_GELU)
-            ops.gemm(u, P[f'{p}.fc2.w'], out=x, bias=P[f'{p}.fc2.b'], residual=x)
+            self._attention_half(ar, i, B, T, x, h, qk, vt, y)
+            if i == L - 1 and defer_tail and self.split:
+                # (the WHOLE batch's buffers: finish_tail addresses rows by their index in the batch; only
+                # the first B * T rows -- the active samples -- were evaluated, and only they are listed)
+                self._deferred = (full['x'], full['y_split'], B * T, C)
+                return x
+            self._tail_half(ar, i, B * T, x, y, h, u)
         return x
 
     def finish_tail(self, rows, n_rows):
@@ -323,8 +383,6 @@ class SamplerNet:
         compact=True -> hidden[i] is row rows[i] (only the first n_rows rows of the list were evaluated)."""
         x, ys, M, C = self._deferred   # (x, ys: the whole batch's buffers; M: the rows that were evaluated)
         self._deferred = None
-        P = self.P
-        p = f"{self.name}.{self.desc['n_layers'] - 1}"
         buf = self._buffers(x.shape[0], C, x.device)
         if 0 < n_rows <= self.TRIM_MAX_ROWS:
             m = int(n_rows)
@@ -334,21 +392,7 @@ class SamplerNet:
         else:
             m, xc, yc, compact = M, x, ys, False
             hc, uc = buf['h_split'], buf['u_split']
-        if self.x8 and self._x8 is not None:
-            i = self.desc['n_layers'] - 1
-            sw, sa = self._x8['w'], self._x8['a']
-            ops.gemm_split(yc, P[f'{p}.proj.w_x8'], m, C, C, out=xc, bias=P[f'{p}.proj.b'], residual=xc,
-                           x8=(sa[i, 'y'], sw[i, 'proj']))
-            ops.layernorm_x8(xc, P[f'{p}.ln2.g'], P[f'{p}.ln2.b'], hc, sa[i, 'h2'])
-            ops.gemm_split(hc, P[f'{p}.fc1.w_x8'], m, 4 * C, C, out_split=uc, bias=P[f'{p}.fc1.b'], act=ACT_GELU,
-                           x8=(sa[i, 'h2'], sw[i, 'fc1']), out_x8_scale=sa[i, 'u'])
-            ops.gemm_split(uc, P[f'{p}.fc2.w_x8'], m, C, 4 * C, out=xc, bias=P[f'{p}.fc2.b'], residual=xc,
-                           x8=(sa[i, 'u'], sw[i, 'fc2']))
-            return xc, compact
-        ops.gemm_split(yc, P[f'{p}.proj.w_split'], m, C, C, out=xc, bias=P[f'{p}.proj.b'], residual=xc)
-        ops.layernorm_split(xc, P[f'{p}.ln2.g'], P[f'{p}.ln2.b'], hc)
-        ops.gemm_split(hc, P[f'{p}.fc1.w_split'], m, 4 * C, C, out_split=uc, bias=P[f'{p}.fc1.b'], act=ACT_GELU)
-        ops.gemm_split(uc, P[f'{p}.fc2.w_split'], m, C, 4 * C, out=xc, bias=P[f'{p}.fc2.b'], residual=xc)
+        self._tail_half(self._arithmetic(), self.desc['n_layers'] - 1, m, xc, yc, hc, uc)
         return xc, compact
 
     def ensure_x8(self):
@@ -404,20 +448,11 @@ class SamplerNet:
         ops.split_overflow(reset=True)
         ops.embed_sum4(idx, segm_tok, tex_tok, P[f'{nm}.tok_emb'], P[f'{nm}.pos_emb'], P[f'{nm}.segm_emb'],
                        P[f'{nm}.tex_emb'], out=x)
+        ar = _Fp16Planes(self)
+        observe = lambda i, role, t, rows, cols: ops.split_rows_absmax(t, rows, cols, bits[slot_a(i, role):])
         for i in range(L):
-            p = f'{nm}.{i}'
-            ops.layernorm_split(x, P[f'{p}.ln1.g'], P[f'{p}.ln1.b'], hs)
-            ops.split_rows_absmax(hs, M, C, bits[slot_a(i, 'h1'):])
-            ops.gemm_split(hs, P[f'{p}.qkv.w_split'], M, 3 * C, C, out_split=qks, bias=P[f'{p}.qkv.b'], vt=vt,
-                           vt_col0=2 * C, vt_T=T, vt_hd=hd)
-            ops.mha_split(qks, 3 * C, vt, B, T, self.n_head, out_split=ys)
-            ops.split_rows_absmax(ys, M, C, bits[slot_a(i, 'y'):])
-            ops.gemm_split(ys, P[f'{p}.proj.w_split'], M, C, C, out=x, bias=P[f'{p}.proj.b'], residual=x)
-            ops.layernorm_split(x, P[f'{p}.ln2.g'], P[f'{p}.ln2.b'], hs)
-            ops.split_rows_absmax(hs, M, C, bits[slot_a(i, 'h2'):])
-            ops.gemm_split(hs, P[f'{p}.fc1.w_split'], M, 4 * C, C, out_split=us, bias=P[f'{p}.fc1.b'], act=ACT_GELU)
-            ops.split_rows_absmax(us, M, 4 * C, bits[slot_a(i, 'u'):])
-            ops.gemm_split(us, P[f'{p}.fc2.w_split'], M, C, 4 * C, out=x, bias=P[f'{p}.fc2.b'], residual=x)
+            self._attention_half(ar, i, B, T, x, hs, qks, vt, ys, observe)
+            self._tail_half(ar, i, M, x, ys, hs, us, observe)
         try:
             check_split_overflow('index sampler (x8 calibration)')
         except SplitOverflowError:

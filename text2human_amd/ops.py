@@ -4,6 +4,7 @@ PyTorch-ROCm is used for device memory, streams and nothing else: every
 function here checks dtype / device / contiguity, takes raw device pointers and
 the current HIP stream, and calls into libt2h_hip.so.
 """
+import collections
 import ctypes
 import os
 
@@ -86,6 +87,9 @@ def gemm_force_config(cfg):
 
 # ---- optional HIP-event profiling of GEMM launches (bench.py roofline leg) ----
 _prof = None
+# one sampled launch: events (e0, e1) around it; kind 'kernel' = the kernel's own start / end, 'stream' = kernel + launch
+# boundary (split GEMM only, with its tile configuration cfg and, 'kernel', the phase-stamp buffer)
+ProfRec = collections.namedtuple('ProfRec', 'label flops e0 e1 kind cfg stamps', defaults=(None, None, None))
 
 
 def gemm_profile_start(every=1):
@@ -145,11 +149,8 @@ def gemm_profile_stop():
 
     blank = lambda label: dict(kernel=label, n=0, ms=0.0, flops=0.0, n_stream=0, ms_stream=0.0, flops_stream=0.0,
                                kernel_timed=False, n_probe=0, loop_us=0.0, loop_ghz=0.0)
-    for rec in p['recs']:
-        label, flops, e0, e1 = rec[:4]
-        kind = rec[4] if len(rec) > 4 else None
-        cfg = rec[5] if len(rec) > 5 else None
-        probe = _probe_clock(rec[6]) if len(rec) > 6 and rec[6] is not None else None
+    for label, flops, e0, e1, kind, cfg, stamps in p['recs']:
+        probe = _probe_clock(stamps) if stamps is not None else None
         r = out.setdefault(label, blank(label))
         add(r, flops, e0, e1, kind, probe)
         if cfg is not None:
@@ -158,22 +159,66 @@ def gemm_profile_stop():
     return out
 
 
-def _launch_gemm(g, what):
-    lib = _lib.load()
-    if _prof is not None:
-        _prof['count'] += 1
-        if _prof['count'] % _prof['every'] == 0:
-            cfg = lib.t2h_gemm_tile_config(ctypes.byref(g))
-            label = (f"gemm_kernel<{GEMM_CFG_NAMES[cfg]},amode={g.a_mode},"
-                     f"pro={int(bool(g.pro_scale))},btrans={g.b_trans}>")
-            flops = 2.0 * g.M * g.N * g.K * max(1, g.batch)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            check(lib.t2h_gemm_f32(ctypes.byref(g), _stream()), what)
-            e1.record()
-            _prof['recs'].append((label, flops, e0, e1))
-            return
-    check(lib.t2h_gemm_f32(ctypes.byref(g), _stream()), what)
+def _sample_phase():
+    """Counts a launch of a profiled family; -> its place in the sampling period (0: sampled), None: profiling is off."""
+    if _prof is None:
+        return None
+    _prof['count'] += 1
+    return _prof['count'] % _prof['every']
+
+
+def _bracketed(fn, args, what, label, flops, kind=None, cfg=None):
+    """The launch fn(*args, stream) between a pair of events on the stream, appended to the profile."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    check(fn(*args, _stream()), what)
+    e1.record()
+    _prof['recs'].append(ProfRec(label, flops, e0, e1, kind, cfg))
+
+
+def _launch(fn, g, what, label, extra=()):
+    """fn(&g, *extra, stream) of a t2h_gemm_args launch; every `every`-th one of a profiling run is bracketed with
+    events and recorded under `label` (a string, or g -> string)."""
+    args = (ctypes.byref(g), *extra)
+    if _sample_phase() != 0:
+        return check(fn(*args, _stream()), what)
+    _bracketed(fn, args, what, label if isinstance(label, str) else label(g), 2.0 * g.M * g.N * g.K * max(1, g.batch))
+
+
+def _gemm_label(g):
+    cfg = _lib.load().t2h_gemm_tile_config(ctypes.byref(g))
+    return f"gemm_kernel<{GEMM_CFG_NAMES[cfg]},amode={g.a_mode},pro={int(bool(g.pro_scale))},btrans={g.b_trans}>"
+
+
+def _gemm_args(a, w, out, M, N, K, lda, ldb, ldc, bias=None, residual=None, act=ACT_NONE, alpha=1.0, res_pre=False):
+    """t2h_gemm_args of one plain GEMM: out[M, N] = act(alpha * a @ w^T + bias) + residual (a tensor's leading
+    dimension is given, not derived: the split-row operands have none)."""
+    g = GemmArgs()
+    g.A, g.B, g.C = a.data_ptr(), w.data_ptr(), out.data_ptr()
+    g.bias = bias.data_ptr() if bias is not None else None
+    g.residual = residual.data_ptr() if residual is not None else None
+    g.M, g.N, g.K = M, N, K
+    g.lda, g.ldb, g.ldc = lda, ldb, ldc
+    g.ldr = _rows(residual) if residual is not None else 0
+    g.epi_act, g.alpha, g.res_pre, g.batch = act, alpha, int(res_pre), 1
+    return g
+
+
+_CONV_MODES = {'same': (1, 1, 0), 'up': (1, 1, 1), 'down': (2, 0, 0)}  # (stride, pad, nearest x2 first)
+
+
+def _conv_args(g, mode, hin, win, cin, pad=None, pro=None, pro_act=PRO_NONE):
+    """... as an implicit convolution over NHWC pixel rows (a_mode 1) -- mode: 'same' (stride 1 pad 1), 'up' (nearest
+    x2 then same conv), 'down' (zero-pad right / bottom by 1, stride 2) --, pro = (scale, shift) [n_img, C] tables
+    applied with pro_act while the operand is staged."""
+    stride, mode_pad, ups = _CONV_MODES[mode]
+    g.a_mode, g.stride, g.pad, g.ups = 1, stride, mode_pad if pad is None else pad, ups
+    g.Hin, g.Win, g.Cin, g.Hout, g.Wout = hin, win, cin, (hin << ups) // stride, (win << ups) // stride
+    if pro is not None:
+        sc, sh = pro
+        _chk_f32(sc, sh)
+        g.pro_scale, g.pro_shift, g.pro_ld, g.pro_act = sc.data_ptr(), sh.data_ptr(), sc.shape[1], pro_act
+    return g
 
 
 def gemm(a, w, out=None, bias=None, residual=None, act=ACT_NONE, alpha=1.0, pro=None,
@@ -189,36 +234,15 @@ def gemm(a, w, out=None, bias=None, residual=None, act=ACT_NONE, alpha=1.0, pro=
     assert (w.shape[0] if b_trans else w.shape[1]) == K, (a.shape, w.shape)
     if out is None:
         out = torch.empty((M, N), device=a.device, dtype=torch.float32)
-    g = GemmArgs()
-    g.A, g.B, g.C = a.data_ptr(), w.data_ptr(), out.data_ptr()
-    g.bias = bias.data_ptr() if bias is not None else None
-    g.residual = residual.data_ptr() if residual is not None else None
-    g.M, g.N, g.K = M, N, K
-    g.lda, g.ldb, g.ldc = _rows(a), _rows(w), _rows(out)
-    g.ldr = _rows(residual) if residual is not None else 0
-    g.a_mode, g.b_trans, g.epi_act, g.alpha = 0, int(b_trans), act, alpha
+    g = _gemm_args(a, w, out, M, N, K, _rows(a), _rows(w), _rows(out), bias, residual, act, alpha)
+    g.b_trans = int(b_trans)
     if pro is not None:
         sc, sh, rows, pact = pro
         _chk_f32(sc, sh)
         g.pro_scale, g.pro_shift = sc.data_ptr(), sh.data_ptr()
         g.pro_rows, g.pro_ld, g.pro_act = rows, sc.shape[1], pact
-    g.batch = 1
-    _launch_gemm(g, 't2h_gemm_f32')
+    _launch(_lib.load().t2h_gemm_f32, g, 't2h_gemm_f32', _gemm_label)
     return out
-
-
-def _launch_conv_split(g, flops):
-    lib = _lib.load()
-    if _prof is not None:
-        _prof['count'] += 1
-        if _prof['count'] % _prof['every'] == 0:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            check(lib.t2h_conv_split_f32(ctypes.byref(g), _stream()), 't2h_conv_split_f32')
-            e1.record()
-            _prof['recs'].append(('conv_split_kernel<2xfp16>', flops, e0, e1))
-            return
-    check(lib.t2h_conv_split_f32(ctypes.byref(g), _stream()), 't2h_conv_split_f32')
 
 
 def conv_split_ok(n_pix_per_img, mode='same', act=ACT_NONE):
@@ -254,24 +278,19 @@ def conv_split(xs, w_split, n_img, hin, win, cin, cout, taps=9, out=None, bias=N
         (tuple(xs.shape), tuple(w_split.shape), n_img, hin, win, cin, cout, taps)
     if out is None:
         out = torch.empty((M, cout), device=xs.device, dtype=torch.float32)
-    g = GemmArgs()
-    g.A, g.B, g.C = xs.data_ptr(), w_split.data_ptr(), out.data_ptr()
-    g.bias = bias.data_ptr() if bias is not None else None
-    g.residual = residual.data_ptr() if residual is not None else None
-    g.M, g.N, g.K = M, cout, taps * cin
-    g.lda, g.ldb, g.ldc = 0, 0, _rows(out)
-    g.ldr = _rows(residual) if residual is not None else 0
-    g.a_mode, g.epi_act, g.alpha, g.res_pre = 1, act, 1.0, int(res_pre)
-    g.Hin, g.Win, g.Cin, g.Hout, g.Wout = hin, win, cin, hout, wout
-    g.stride, g.pad, g.ups, g.batch = 1, (1 if taps == 9 else 0), ups, 1
-    part = None
-    if gn_stats:  # per-(image, 128-row tile, channel) fp64 (sum, sum of squares) of the output, from the epilogue
-        part = torch.empty((n_img, hout * wout // 128, 2, cout), device=xs.device, dtype=torch.float64)
-        g.gn_part_out = part.data_ptr()
-    _launch_conv_split(g, 2.0 * M * cout * taps * cin)
-    if part is not None:
-        out._t2h_gn_part = part  # groupnorm_tables(out, ...) then only reduces these partials
+    g = _conv_args(_gemm_args(xs, w_split, out, M, cout, taps * cin, 0, 0, _rows(out), bias, residual, act,
+                              res_pre=res_pre), mode, hin, win, cin, pad=1 if taps == 9 else 0)
+    if gn_stats:
+        _gn_part(g, out, n_img, hout * wout)
+    _launch(_lib.load().t2h_conv_split_f32, g, 't2h_conv_split_f32', 'conv_split_kernel<2xfp16>')
     return out
+
+
+def _gn_part(g, out, n_img, hw_out):
+    """per-(image, 128-row tile, channel) fp64 (sum, sum of squares) of a convolution's output, written by its
+    epilogue; attached to `out`: groupnorm_tables(out, ...) then only reduces these partials"""
+    out._t2h_gn_part = torch.empty((n_img, hw_out // 128, 2, g.N), device=out.device, dtype=torch.float64)
+    g.gn_part_out = out._t2h_gn_part.data_ptr()
 
 
 def conv_halo_ok(n_img, hout, wout, cin, cout, mode='same'):
@@ -306,40 +325,11 @@ def conv_halo(x, w_split, n_img, hin, win, cin, cout, out=None, bias=None, resid
         (tuple(x.shape), tuple(w_split.shape), n_img, hin, win, cin, cout)
     if out is None:
         out = torch.empty((M, cout), device=x.device, dtype=torch.float32)
-    g = GemmArgs()
-    g.A, g.B, g.C = x.data_ptr(), w_split.data_ptr(), out.data_ptr()
-    g.bias = bias.data_ptr() if bias is not None else None
-    g.residual = residual.data_ptr() if residual is not None else None
-    g.M, g.N, g.K = M, cout, 9 * cin
-    g.lda, g.ldb, g.ldc = _rows(x), 0, _rows(out)
-    g.ldr = _rows(residual) if residual is not None else 0
-    g.a_mode, g.epi_act, g.alpha, g.res_pre = 1, ACT_NONE, 1.0, 0
-    g.Hin, g.Win, g.Cin, g.Hout, g.Wout = hin, win, cin, hout, wout
-    g.stride, g.pad, g.ups, g.batch = 1, 1, ups, 1
-    if pro is not None:
-        sc, sh = pro
-        _chk_f32(sc, sh)
-        g.pro_scale, g.pro_shift, g.pro_ld, g.pro_act = sc.data_ptr(), sh.data_ptr(), sc.shape[1], PRO_SWISH
-    part = None
+    g = _conv_args(_gemm_args(x, w_split, out, M, cout, 9 * cin, _rows(x), 0, _rows(out), bias, residual),
+                   mode, hin, win, cin, pro=pro, pro_act=PRO_SWISH)
     if gn_stats:
-        part = torch.empty((n_img, hout * wout // 128, 2, cout), device=x.device, dtype=torch.float64)
-        g.gn_part_out = part.data_ptr()
-    lib = _lib.load()
-    flops = 2.0 * M * cout * 9 * cin
-    if _prof is not None:
-        _prof['count'] += 1
-        if _prof['count'] % _prof['every'] == 0:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            check(lib.t2h_conv_halo_f32(ctypes.byref(g), overflow_flag(), _stream()), 't2h_conv_halo_f32')
-            e1.record()
-            _prof['recs'].append(('conv_halo_kernel<2xfp16>', flops, e0, e1))
-            if part is not None:
-                out._t2h_gn_part = part
-            return out
-    check(lib.t2h_conv_halo_f32(ctypes.byref(g), overflow_flag(), _stream()), 't2h_conv_halo_f32')
-    if part is not None:
-        out._t2h_gn_part = part
+        _gn_part(g, out, n_img, hout * wout)
+    _launch(_lib.load().t2h_conv_halo_f32, g, 't2h_conv_halo_f32', 'conv_halo_kernel<2xfp16>', (overflow_flag(), ))
     return out
 
 
@@ -349,14 +339,11 @@ def bgemm(a, w, out, alpha=1.0, b_trans=False):
     _chk_f32(a, w, out)
     nb, M, K = a.shape
     N = w.shape[2] if b_trans else w.shape[1]
-    g = GemmArgs()
-    g.A, g.B, g.C = a.data_ptr(), w.data_ptr(), out.data_ptr()
-    g.M, g.N, g.K = M, N, K
     assert a.stride(2) == 1 and w.stride(2) == 1 and out.stride(2) == 1
-    g.lda, g.ldb, g.ldc = a.stride(1), w.stride(1), out.stride(1)
+    g = _gemm_args(a, w, out, M, N, K, a.stride(1), w.stride(1), out.stride(1), alpha=alpha)
     g.strideA, g.strideB, g.strideC = a.stride(0), w.stride(0), out.stride(0)
-    g.batch, g.alpha, g.b_trans = nb, alpha, int(b_trans)
-    _launch_gemm(g, 't2h_gemm_f32(batched)')
+    g.batch, g.b_trans = nb, int(b_trans)
+    _launch(_lib.load().t2h_gemm_f32, g, 't2h_gemm_f32(batched)', _gemm_label)
     return out
 
 
@@ -370,33 +357,16 @@ def conv3x3(x, w, n_img, hin, win, cin, out=None, bias=None, residual=None, act=
     ksplit: K slices on their own workgroups (t2h_gemm_args.ksplit): None = the library's choice from the layer's
           geometry (few pixels per image: the deep UNet levels), 1 = one pass over K, n > 1 = n slices."""
     _chk_f32(x, w, out, bias, residual)
-    if mode == 'same':
-        hout, wout, stride, pad, ups = hin, win, 1, 1, 0
-    elif mode == 'up':
-        hout, wout, stride, pad, ups = 2 * hin, 2 * win, 1, 1, 1
-    elif mode == 'down':
-        hout, wout, stride, pad, ups = hin // 2, win // 2, 2, 0, 0
-    else:
+    if mode not in _CONV_MODES:
         raise ValueError(mode)
-    M, N = n_img * hout * wout, w.shape[0]
+    stride, _, ups = _CONV_MODES[mode]
+    M, N = n_img * ((hin << ups) // stride) * ((win << ups) // stride), w.shape[0]
     assert w.shape[1] == 9 * cin and x.shape[0] == n_img * hin * win
     if out is None:
         out = torch.empty((M, N), device=x.device, dtype=torch.float32)
-    g = GemmArgs()
-    g.A, g.B, g.C = x.data_ptr(), w.data_ptr(), out.data_ptr()
-    g.bias = bias.data_ptr() if bias is not None else None
-    g.residual = residual.data_ptr() if residual is not None else None
-    g.M, g.N, g.K = M, N, 9 * cin
-    g.lda, g.ldb, g.ldc = _rows(x), _rows(w), _rows(out)
-    g.ldr = _rows(residual) if residual is not None else 0
-    g.a_mode, g.epi_act, g.alpha, g.res_pre = 1, act, 1.0, int(res_pre)
-    g.Hin, g.Win, g.Cin, g.Hout, g.Wout = hin, win, cin, hout, wout
-    g.stride, g.pad, g.ups, g.batch = stride, pad, ups, 1
-    if pro is not None:
-        sc, sh, pact = pro
-        _chk_f32(sc, sh)
-        g.pro_scale, g.pro_shift = sc.data_ptr(), sh.data_ptr()
-        g.pro_ld, g.pro_act = sc.shape[1], pact
+    g = _conv_args(_gemm_args(x, w, out, M, N, 9 * cin, _rows(x), _rows(w), _rows(out), bias, residual, act,
+                              res_pre=res_pre), mode, hin, win, cin, pro=pro[:2] if pro is not None else None,
+                   pro_act=pro[2] if pro is not None else PRO_NONE)
     # few pixels per image (the deep UNet levels): K split across workgroups, partial tiles in a workspace of this
     # call (stream-ordered like every torch allocation); the slice count depends on the layer's geometry only
     if ksplit is None:
@@ -408,7 +378,7 @@ def conv3x3(x, w, n_img, hin, win, cin, out=None, bias=None, residual=None, act=
         g.splitk_ws, g.splitk_ws_floats, g.ksplit = ws.data_ptr(), ws.numel(), int(ksplit)
     else:
         g.ksplit = 1
-    _launch_gemm(g, 't2h_gemm_f32(conv)')
+    _launch(_lib.load().t2h_gemm_f32, g, 't2h_gemm_f32(conv)', _gemm_label)
     return out
 
 
@@ -585,36 +555,28 @@ def gemm_split(a_split, w_split, M, N, K, out=None, out_split=None, bias=None, r
     if out_split is not None or vt is not None:
         g.overflow_flag = _ovf_slot()[0].data_ptr()
     lib = _lib.load()
-    if _prof is not None:
-        _prof['count'] += 1
-        phase = _prof['count'] % _prof['every']
-        # algorithmic (fp32-equivalent) FLOPs; the kernel issues 3 fp16 products per multiply.  Two kinds of
-        # samples, on DIFFERENT launches (timing a kernel through hipExtLaunchKernelGGL adds packets around it):
-        if phase == 0 or phase == _prof['every'] // 2:
-            cfg = lib.t2h_gemm_split_tile_config(ctypes.byref(g))
-        if phase == 0:
-            # (k0, k1) receive the kernel's OWN start / end (t2h_gemm_split_time_next_launch): kernel time; the same
-            # launch stores its phase stamps (main loop duration + the shader clock it ran at)
-            k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            k0.record()  # (creates the hipEvent_t handles the hook hands to the launch)
-            k1.record()
-            # (sized for the smallest tile any configuration uses, 64 x 64: the kernel stores 16 words per workgroup unbounded)
-            stamps = torch.zeros(16 * (-(-M // 64)) * (-(-N // 64)), dtype=torch.int64, device=a_split.device)
-            check(lib.t2h_gemm_split_time_next_launch(ctypes.c_void_p(k0.cuda_event), ctypes.c_void_p(k1.cuda_event)),
-                  't2h_gemm_split_time_next_launch')
-            check(lib.t2h_gemm_split_probe_next_launch(_p(stamps)), 't2h_gemm_split_probe_next_launch')
-            check(lib.t2h_gemm_split_f32(ctypes.byref(g), _stream()), 't2h_gemm_split_f32')
-            _prof['recs'].append((_split_label(g), 2.0 * M * N * K, k0, k1, 'kernel', cfg, stamps))
-            return out if out is not None else out_split
-        if phase == _prof['every'] // 2:
-            # (e0, e1) are recorded on the stream around the launch and so run from the end of the previous
+    phase = _sample_phase()
+    # algorithmic (fp32-equivalent) FLOPs; the kernel issues 3 fp16 products per multiply.  Two kinds of
+    # samples, on DIFFERENT launches (timing a kernel through hipExtLaunchKernelGGL adds packets around it):
+    if phase is not None and phase in (0, _prof['every'] // 2):
+        cfg = lib.t2h_gemm_split_tile_config(ctypes.byref(g))
+        if phase != 0:
+            # events recorded on the stream around the launch, which so run from the end of the previous
             # kernel: kernel + dependent-launch boundary
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            check(lib.t2h_gemm_split_f32(ctypes.byref(g), _stream()), 't2h_gemm_split_f32')
-            e1.record()
-            _prof['recs'].append((_split_label(g), 2.0 * M * N * K, e0, e1, 'stream', cfg, None))
+            _bracketed(lib.t2h_gemm_split_f32, (ctypes.byref(g), ), 't2h_gemm_split_f32', _split_label(g),
+                       2.0 * M * N * K, 'stream', cfg)
             return out if out is not None else out_split
+        # (k0, k1) receive the kernel's OWN start / end (t2h_gemm_split_time_next_launch): kernel time; the same
+        # launch stores its phase stamps (main loop duration + the shader clock it ran at)
+        k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        k0.record()  # (creates the hipEvent_t handles the hook hands to the launch)
+        k1.record()
+        # (sized for the smallest tile any configuration uses, 64 x 64: the kernel stores 16 words per workgroup unbounded)
+        stamps = torch.zeros(16 * (-(-M // 64)) * (-(-N // 64)), dtype=torch.int64, device=a_split.device)
+        check(lib.t2h_gemm_split_time_next_launch(ctypes.c_void_p(k0.cuda_event), ctypes.c_void_p(k1.cuda_event)),
+              't2h_gemm_split_time_next_launch')
+        check(lib.t2h_gemm_split_probe_next_launch(_p(stamps)), 't2h_gemm_split_probe_next_launch')
+        _prof['recs'].append(ProfRec(_split_label(g), 2.0 * M * N * K, k0, k1, 'kernel', cfg, stamps))
     check(lib.t2h_gemm_split_f32(ctypes.byref(g), _stream()), 't2h_gemm_split_f32')
     return out if out is not None else out_split
 
