@@ -419,6 +419,66 @@ int t2h_schedule_advance(const int32_t* rows_tbl, const int64_t* aux64_tbl, cons
                          int32_t maxr, void* stream);
 int t2h_sample_heads(const t2h_sample_heads_args* args, void* stream);
 
+/* Confidence-ordered parallel decoding ("Confidence-ordered decoding"): every round draws a token for EVERY
+ * still-masked row (x_t[row] == mask_id), with the confidence of the draw, and commits the k best per sample.
+ *
+ * t2h_confidence_tail: for every masked row, logits l = head_tex(LN_f(hidden[row])) / temp -- each logit the same
+ *   per-lane fma chain + wave butterfly as t2h_sample_heads, so the drawn token is the one that entry point draws on
+ *   the same noise -- then tok[row] = argmax_j exp(l_j - max l) / E[row][j] (first index wins) and
+ *   conf[row] = l_tok - max l - log(sum_j exp(l_j - max l)).  Rows that are not masked (or whose texture id is outside
+ *   [0, n_heads)) get tok = -1, conf = -inf.  x_t is only read.  Three launches: the masked rows are grouped by head
+ *   on the device into tiles of 16 rows that share one stream of the head's weights (group_ws), the logits go to
+ *   logits_ws [n][n_class], one wave per row picks.  Noise: expo [n][n_class] explicit, or (expo NULL) the elements of
+ *   torch's `empty(n, n_class).exponential_()` at generator (seed, offset); seed / offset are read from device memory
+ *   where the *_dev pointer is set (a round replayed with other values).
+ *   group_ws: int32 [t2h_confidence_group_ws_ints(n, n_heads)].
+ * t2h_confidence_commit: one workgroup per sample.  score s = conf + tau * g, g = -log(-log(u)), u = U[row] clamped to
+ *   [2^-24, 1 - 2^-24] (U explicit [n], or NULL: the elements of torch's `rand(n)` at (seed, offset)); the k[b] masked
+ *   rows of sample b with the largest s (equal scores: lower row first; NaN below every number) are committed:
+ *   x_t[row] = tok[row] + n_class * tex[row], out[tex[row]][row] = tok[row].  scores [n] (optional) receives s
+ *   (-inf for rows that are not masked).  k int32 [B] and tau float [1] live in device memory (the staging buffers of
+ *   t2h_schedule_advance).  T <= 2048. */
+typedef struct t2h_confidence_tail_args {
+  const float* hidden;      /* [n][C] */
+  const float* lnf_gamma;
+  const float* lnf_beta;
+  const float* w_heads;     /* [n_heads][n_class][C] */
+  const int64_t* tex;       /* [n] */
+  const int64_t* x_t;       /* [n] */
+  int64_t mask_id;
+  float temp;
+  int32_t n, C, n_class, n_heads;
+  const float* expo;
+  uint64_t philox_seed, philox_offset;
+  const uint64_t* philox_seed_dev;
+  const uint64_t* philox_offset_dev;
+  uint32_t philox_grid_threads;
+  int32_t* group_ws;
+  float* logits_ws;
+  int32_t* tok;             /* [n] */
+  float* conf;              /* [n] */
+} t2h_confidence_tail_args;
+typedef struct t2h_confidence_commit_args {
+  const float* conf;
+  const int32_t* tok;
+  const int64_t* tex;
+  const float* u;
+  uint64_t philox_seed, philox_offset;
+  const uint64_t* philox_seed_dev;
+  const uint64_t* philox_offset_dev;
+  uint32_t philox_grid_threads;
+  const int32_t* k;
+  const float* tau;
+  int64_t mask_id;
+  int64_t* x_t;             /* [B][T] */
+  int64_t* out;             /* [n_heads][B * T] */
+  float* scores;
+  int32_t B, T, n_heads, n_class;
+} t2h_confidence_commit_args;
+int64_t t2h_confidence_group_ws_ints(int32_t n, int32_t n_heads);
+int t2h_confidence_tail(const t2h_confidence_tail_args* args, void* stream);
+int t2h_confidence_commit(const t2h_confidence_commit_args* args, void* stream);
+
 /* Sampler training-time forward (models/transformer_model.py:212-274, forward only).
  * q_sample: mask[b,i] = u[b,i] < t[b] / num_timesteps; x_t = mask ? mask_id : x0.
  * masked_ce_heads: sum over the 18 heads of F.cross_entropy(logits_h, gt_h, ignore_index=-1,

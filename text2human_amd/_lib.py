@@ -64,6 +64,28 @@ class SampleHeadsArgs(ctypes.Structure):
     ]
 
 
+class ConfidenceTailArgs(ctypes.Structure):
+    """struct t2h_confidence_tail_args (include/t2h_hip.h)."""
+    _fields_ = [
+        ('hidden', c_vp), ('lnf_gamma', c_vp), ('lnf_beta', c_vp), ('w_heads', c_vp), ('tex', c_vp), ('x_t', c_vp),
+        ('mask_id', c_i64), ('temp', c_f32), ('n', c_i32), ('C', c_i32), ('n_class', c_i32), ('n_heads', c_i32),
+        ('expo', c_vp), ('philox_seed', ctypes.c_uint64), ('philox_offset', ctypes.c_uint64),
+        ('philox_seed_dev', c_vp), ('philox_offset_dev', c_vp), ('philox_grid_threads', ctypes.c_uint32),
+        ('group_ws', c_vp), ('logits_ws', c_vp), ('tok', c_vp), ('conf', c_vp),
+    ]
+
+
+class ConfidenceCommitArgs(ctypes.Structure):
+    """struct t2h_confidence_commit_args (include/t2h_hip.h)."""
+    _fields_ = [
+        ('conf', c_vp), ('tok', c_vp), ('tex', c_vp), ('u', c_vp),
+        ('philox_seed', ctypes.c_uint64), ('philox_offset', ctypes.c_uint64),
+        ('philox_seed_dev', c_vp), ('philox_offset_dev', c_vp), ('philox_grid_threads', ctypes.c_uint32),
+        ('k', c_vp), ('tau', c_vp), ('mask_id', c_i64), ('x_t', c_vp), ('out', c_vp), ('scores', c_vp),
+        ('B', c_i32), ('T', c_i32), ('n_heads', c_i32), ('n_class', c_i32),
+    ]
+
+
 # name -> (restype, argtypes); must list EVERY symbol declared in include/t2h_hip.h
 SIGNATURES = {
     't2h_gemm_split_f32': (ctypes.c_int, [ctypes.POINTER(GemmSplitArgs), c_vp]),
@@ -104,6 +126,9 @@ SIGNATURES = {
     't2h_mha_noncausal_f32': (ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
     't2h_unmask_step': (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp]),
     't2h_sample_heads': (ctypes.c_int, [ctypes.POINTER(SampleHeadsArgs), c_vp]),
+    't2h_confidence_group_ws_ints': (c_i64, [c_i32, c_i32]),
+    't2h_confidence_tail': (ctypes.c_int, [ctypes.POINTER(ConfidenceTailArgs), c_vp]),
+    't2h_confidence_commit': (ctypes.c_int, [ctypes.POINTER(ConfidenceCommitArgs), c_vp]),
     't2h_absmax_f32': (ctypes.c_int, [c_vp, c_i32, c_i64, c_i32, c_vp, c_vp]),
     't2h_split_rows_absmax': (ctypes.c_int, [c_vp, c_i64, c_i32, c_vp, c_vp]),
     't2h_gather_rows': (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]),

@@ -630,7 +630,265 @@ __global__ __launch_bounds__(SH_THREADS) void sample_heads_kernel(const t2h_samp
                 a.temp, a.x_t, a.out_idx + (int64_t)head * a.n, a.n_class);  // (full hidden only)
 }
 
+// ---- confidence-ordered parallel decoding ("Confidence-ordered decoding").  A round samples EVERY masked
+// row -- up to B * 512 rows instead of a few dozen -- so the head GEMV of the tail above (2 MB of weights per row) is
+// the wrong shape: the masked rows are grouped by head, CT_ROWS rows of one head share one stream of its weights.
+// Every logit is still the per-lane fma chain + wave butterfly of sample_row (the LayerNorm'ed row now comes from LDS
+// instead of registers), so the logits, and the token the race draws, are the bits of t2h_sample_heads.
+constexpr int CT_ROWS = 16, CT_SPLIT = 4, CT_THREADS = 256, CT_HDR = 4;
+
+__host__ __device__ inline int conf_max_tiles(int n, int n_heads) { return (n + CT_ROWS - 1) / CT_ROWS + n_heads; }
+
+// group_ws: [0] = number of tiles, [1] = number of masked rows, tiles {head, first slot, rows} from CT_HDR on, then the
+// masked rows sorted by head.  (The order of a head's rows is whatever the atomics give: no result depends on it.)
+__global__ __launch_bounds__(1024) void conf_group_kernel(const int64_t* __restrict__ x_t, const int64_t* __restrict__ tex,
+                                                          int64_t mask_id, int n, int n_heads, int32_t* __restrict__ ws) {
+  __shared__ int cnt[T2H_MAX_HEADS], first[T2H_MAX_HEADS], cur[T2H_MAX_HEADS];
+  const int tid = threadIdx.x;
+  const int max_tiles = conf_max_tiles(n, n_heads);
+  int32_t* tiles = ws + CT_HDR;
+  int32_t* rows = tiles + 3 * max_tiles;
+  if (tid < T2H_MAX_HEADS) cnt[tid] = cur[tid] = 0;
+  __syncthreads();
+  for (int e = tid; e < n; e += blockDim.x) {
+    const int h = (int)tex[e];
+    if (x_t[e] == mask_id && h >= 0 && h < n_heads) atomicAdd(&cnt[h], 1);
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int s = 0, t = 0;
+    for (int h = 0; h < n_heads; ++h) {
+      first[h] = s;
+      for (int o = 0; o < cnt[h] && t < max_tiles; o += CT_ROWS, ++t) {
+        tiles[3 * t] = h;
+        tiles[3 * t + 1] = s + o;
+        tiles[3 * t + 2] = min(CT_ROWS, cnt[h] - o);
+      }
+      s += cnt[h];
+    }
+    ws[0] = t;
+    ws[1] = s;
+  }
+  __syncthreads();
+  for (int e = tid; e < n; e += blockDim.x) {
+    const int h = (int)tex[e];
+    if (x_t[e] == mask_id && h >= 0 && h < n_heads) rows[first[h] + atomicAdd(&cur[h], 1)] = e;
+  }
+}
+
+// One workgroup per (tile, class quarter): LN_f of the tile's rows into LDS (one wave per row, the arithmetic of
+// sample_row), then every wave streams 4 weight rows at a time and uses them for all rows of the tile.
+template <int C>
+__global__ __launch_bounds__(CT_THREADS) void conf_logits_kernel(const t2h_confidence_tail_args a) {
+  constexpr int VPL = C / 256, NW = CT_THREADS / 64;
+  __shared__ __attribute__((aligned(16))) float xs[CT_ROWS * C];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tile = blockIdx.x / CT_SPLIT, part = blockIdx.x - tile * CT_SPLIT;
+  const int32_t* ws = a.group_ws;
+  if (tile >= ws[0]) return;  // (uniform over the workgroup)
+  const int32_t* td = ws + CT_HDR + 3 * tile;
+  const int head = td[0], cnt = min(td[2], CT_ROWS);
+  const int32_t* rows = ws + CT_HDR + 3 * conf_max_tiles(a.n, a.n_heads) + td[1];
+  for (int r = wave; r < cnt; r += NW) {
+    const float* xr = a.hidden + (int64_t)rows[r] * C;
+    f32x4 v[VPL];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+      v[i] = *reinterpret_cast<const f32x4*>(xr + i * 256 + lane * 4);
+      s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
+    }
+    const float mean = wave_sum(s) * (1.0f / C);
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < VPL; ++i)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float d = v[i][e] - mean;
+        q = fmaf(d, d, q);
+      }
+    const float rstd = 1.0f / sqrtf(wave_sum(q) * (1.0f / C) + 1e-5f);
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+      const f32x4 gg = *reinterpret_cast<const f32x4*>(a.lnf_gamma + i * 256 + lane * 4);
+      const f32x4 bb = *reinterpret_cast<const f32x4*>(a.lnf_beta + i * 256 + lane * 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[i][e] = (v[i][e] - mean) * rstd * gg[e] + bb[e];
+      *reinterpret_cast<f32x4*>(xs + r * C + i * 256 + lane * 4) = v[i];
+    }
+  }
+  __syncthreads();
+  const float temp = a.temp;
+  const float* w = a.w_heads + (int64_t)head * a.n_class * C;
+  const int per = (a.n_class + CT_SPLIT - 1) / CT_SPLIT;
+  const int j_end = min(a.n_class, (part + 1) * per);
+  for (int j0 = part * per + wave * 4; j0 < j_end; j0 += NW * 4) {
+    f32x4 ww[4][VPL];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const float* wr = w + (int64_t)min(j0 + u, a.n_class - 1) * C;
+#pragma unroll
+      for (int i = 0; i < VPL; ++i) ww[u][i] = *reinterpret_cast<const f32x4*>(wr + i * 256 + lane * 4);
+    }
+    for (int r = 0; r < cnt; ++r) {
+      f32x4 v[VPL];
+#pragma unroll
+      for (int i = 0; i < VPL; ++i) v[i] = *reinterpret_cast<const f32x4*>(xs + r * C + i * 256 + lane * 4);
+      float acc[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        float t = 0.f;
+#pragma unroll
+        for (int i = 0; i < VPL; ++i)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) t = fmaf(ww[u][i][e], v[i][e], t);
+        acc[u] = t;
+      }
+      float* lg = a.logits_ws + (int64_t)rows[r] * a.n_class;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const float res = wave_sum(acc[u]);
+        if (lane == 0 && j0 + u < j_end) lg[j0 + u] = res / temp;
+      }
+    }
+  }
+}
+
+// One wave per row: max, the exponential race of sample_pick_kernel (same scores, lowest index of the maximum), the
+// sum of the same exponentials, and the log-probability of the drawn class.
+constexpr int CP_ROWS = 4;
+__global__ __launch_bounds__(64 * CP_ROWS) void conf_pick_kernel(const t2h_confidence_tail_args a) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * CP_ROWS + (threadIdx.x >> 6);
+  if (row >= a.n) return;  // (uniform over the wave)
+  const int head = (int)a.tex[row];
+  if (a.x_t[row] != a.mask_id || head < 0 || head >= a.n_heads) {
+    if (lane == 0) {
+      a.tok[row] = -1;
+      a.conf[row] = -INFINITY;
+    }
+    return;
+  }
+  const float* lg = a.logits_ws + (int64_t)row * a.n_class;
+  float mx = -INFINITY;
+  for (int j = lane; j < a.n_class; j += 64) mx = fmaxf(mx, lg[j]);
+  mx = wave_max(mx);
+  const float* er = a.expo ? a.expo + (int64_t)row * a.n_class : nullptr;
+  const uint64_t pseed = a.philox_seed_dev ? *a.philox_seed_dev : a.philox_seed;
+  const uint64_t poff = a.philox_offset_dev ? *a.philox_offset_dev : a.philox_offset;
+  float best = -1.f, se = 0.f;
+  int best_j = 0x7fffffff;
+  for (int j = lane; j < a.n_class; j += 64) {
+    const float q = er ? er[j] : torch_exponential_at(pseed, poff, a.philox_grid_threads, (uint64_t)row * a.n_class + j);
+    const float ex = expf(lg[j] - mx);
+    const float sc = ex / q;
+    se += ex;
+    if (sc > best) {
+      best = sc;
+      best_j = j;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ob = __shfl_xor(best, o, 64);
+    const int oj = __shfl_xor(best_j, o, 64);
+    if (ob > best || (ob == best && oj < best_j)) {
+      best = ob;
+      best_j = oj;
+    }
+  }
+  se = wave_sum(se);
+  if (lane == 0) {
+    if (best_j >= a.n_class) best_j = 0;  // all-NaN scores: see sample_row
+    a.tok[row] = best_j;
+    a.conf[row] = (lg[best_j] - mx) - logf(se);
+  }
+}
+
+// One workgroup per sample: scores into LDS, rank of every masked row by counting, the k best commit.
+constexpr int CC_THREADS = 512, CC_MAX_T = 2048;
+__device__ __forceinline__ bool conf_before(float sj, int j, float si, int i) {  // row j ranks before row i
+  const bool nj = sj != sj, ni = si != si;
+  if (nj || ni) return nj == ni ? j < i : ni;
+  return sj > si || (sj == si && j < i);
+}
+__global__ __launch_bounds__(CC_THREADS) void conf_commit_kernel(const t2h_confidence_commit_args a) {
+  __shared__ float s_s[CC_MAX_T];
+  __shared__ int m_s[CC_MAX_T];
+  const int b = blockIdx.x, tid = threadIdx.x, T = a.T;
+  const int k = a.k[b];
+  const float tau = *a.tau;
+  const uint64_t pseed = a.philox_seed_dev ? *a.philox_seed_dev : a.philox_seed;
+  const uint64_t poff = a.philox_offset_dev ? *a.philox_offset_dev : a.philox_offset;
+  for (int i = tid; i < T; i += CC_THREADS) {
+    const int64_t row = (int64_t)b * T + i;
+    const int64_t h = a.tex[row];
+    const bool masked = a.x_t[row] == a.mask_id && a.tok[row] >= 0 && a.tok[row] < a.n_class && h >= 0 && h < a.n_heads;
+    float s = -INFINITY;
+    if (masked) {
+      float u = a.u ? a.u[row] : torch_uniform_at(pseed, poff, a.philox_grid_threads, (uint64_t)row);
+      u = fminf(fmaxf(u, 5.9604644775390625e-8f), 1.0f - 5.9604644775390625e-8f);
+      const float g = -logf(-logf(u));
+      s = __fadd_rn(a.conf[row], __fmul_rn(tau, g));
+    }
+    s_s[i] = s;
+    m_s[i] = masked ? 1 : 0;
+    if (a.scores) a.scores[row] = s;
+  }
+  __syncthreads();
+  for (int i = tid; i < T; i += CC_THREADS) {
+    if (!m_s[i]) continue;
+    const float si = s_s[i];
+    int rank = 0;
+    for (int j = 0; j < T; ++j) rank += (m_s[j] && j != i && conf_before(s_s[j], j, si, i)) ? 1 : 0;
+    if (rank < k) {
+      const int64_t row = (int64_t)b * T + i;
+      const int64_t tk = a.tok[row], h = a.tex[row];
+      a.x_t[row] = tk + (int64_t)a.n_class * h;
+      a.out[h * ((int64_t)a.B * T) + row] = tk;
+    }
+  }
+}
+
 }  // namespace
+
+extern "C" int64_t t2h_confidence_group_ws_ints(int32_t n, int32_t n_heads) {
+  if (n <= 0 || n_heads <= 0) return 0;
+  return (int64_t)CT_HDR + 3 * (int64_t)conf_max_tiles(n, n_heads) + n;
+}
+
+extern "C" int t2h_confidence_tail(const t2h_confidence_tail_args* args, void* stream) {
+  T2H_REQUIRE(args != nullptr, "t2h_confidence_tail: args is NULL");
+  const t2h_confidence_tail_args a = *args;
+  T2H_REQUIRE(a.hidden && a.lnf_gamma && a.lnf_beta && a.w_heads && a.tex && a.x_t && a.group_ws && a.logits_ws &&
+                  a.tok && a.conf,
+              "t2h_confidence_tail: NULL pointer");
+  T2H_REQUIRE(a.n > 0 && a.n_class > 0 && a.temp > 0.f && a.n_heads > 0 && a.n_heads <= T2H_MAX_HEADS &&
+                  (int64_t)a.n * a.n_class < ((int64_t)1 << 40),
+              "t2h_confidence_tail: bad arguments");
+  T2H_REQUIRE(a.C == 512, "t2h_confidence_tail: C=%d unsupported (512)", a.C);
+  T2H_REQUIRE(a.expo != nullptr || (a.philox_grid_threads != 0 && (a.philox_offset_dev || a.philox_offset % 4 == 0)),
+              "t2h_confidence_tail: no noise (expo, or philox_grid_threads and an offset that is a multiple of 4)");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(conf_group_kernel, dim3(1), dim3(1024), 0, s, a.x_t, a.tex, a.mask_id, a.n, a.n_heads, a.group_ws);
+  hipLaunchKernelGGL(conf_logits_kernel<512>, dim3(conf_max_tiles(a.n, a.n_heads) * CT_SPLIT), dim3(CT_THREADS), 0, s, a);
+  hipLaunchKernelGGL(conf_pick_kernel, dim3((a.n + CP_ROWS - 1) / CP_ROWS), dim3(64 * CP_ROWS), 0, s, a);
+  T2H_CHECK_LAUNCH("t2h_confidence_tail");
+  return T2H_OK;
+}
+
+extern "C" int t2h_confidence_commit(const t2h_confidence_commit_args* args, void* stream) {
+  T2H_REQUIRE(args != nullptr, "t2h_confidence_commit: args is NULL");
+  const t2h_confidence_commit_args a = *args;
+  T2H_REQUIRE(a.conf && a.tok && a.tex && a.k && a.tau && a.x_t && a.out, "t2h_confidence_commit: NULL pointer");
+  T2H_REQUIRE(a.B > 0 && a.T > 0 && a.T <= CC_MAX_T && a.n_heads > 0 && a.n_heads <= T2H_MAX_HEADS && a.n_class > 0,
+              "t2h_confidence_commit: bad arguments (B=%d T=%d)", a.B, a.T);
+  T2H_REQUIRE(a.u != nullptr || (a.philox_grid_threads != 0 && (a.philox_offset_dev || a.philox_offset % 4 == 0)),
+              "t2h_confidence_commit: no noise (u, or philox_grid_threads and an offset that is a multiple of 4)");
+  hipLaunchKernelGGL(conf_commit_kernel, dim3(a.B), dim3(CC_THREADS), 0, static_cast<hipStream_t>(stream), a);
+  T2H_CHECK_LAUNCH("t2h_confidence_commit");
+  return T2H_OK;
+}
 
 extern "C" int t2h_embed_sum4_f32(const int64_t* idx, const int64_t* segm, const int64_t* tex,
                                   const float* tok_emb, const float* pos_emb, const float* segm_emb,

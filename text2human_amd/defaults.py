@@ -125,6 +125,15 @@ def sampler(ckpt_dir='./pretrained_models'):
     return o
 
 
+def with_confidence_order(opt, rounds=16, choice_temp=4.5):
+    """`opt` with the keys that switch sample_and_refine / inference to confidence-ordered decoding
+    (options.sampling_order; without them the reference's loop runs).  Returns opt."""
+    opt['sample_order'] = 'confidence'
+    opt['confidence_rounds'] = int(rounds)
+    opt['confidence_choice_temp'] = float(choice_temp)
+    return opt
+
+
 def write_yaml(opt, path):
     with open(path, 'w') as f:
         yaml.safe_dump(dict(opt), f, sort_keys=False)

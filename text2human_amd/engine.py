@@ -912,6 +912,114 @@ def sample_tokens(net, segm_tok, tex_tok, sample_steps, mask_id, temp=1.0, noise
     return in_batch_order(out)
 
 
+def sample_tokens_confidence(net, segm_tok, tex_tok, mask_id, rounds=16, temp=1.0, choice_temp=4.5, noise=None,
+                             n_books=18, round_hook=None, init=None):
+    """Confidence-ordered parallel decoding ("Confidence-ordered decoding"; opt-in, sample_tokens is the
+    reference's loop): `rounds` rounds, each ONE transformer evaluation of the whole batch, a token + confidence for
+    every still-masked row (t2h_confidence_tail) and, per sample, the commit of the k_r rows with the largest score
+    conf + tau_r * gumbel (t2h_confidence_commit).  k_r (schedule.confidence_schedule, from every sample's own number
+    of masked rows), tau_r and the generator offsets of the round's two draws sit in device tables that
+    t2h_schedule_advance walks, so a round is the same launch sequence with the same arguments every time and the loop
+    reads nothing back.  Per round the device generator is consumed as `empty(B*T, n_class).exponential_()` then
+    `rand(B*T)` would consume it (the elements needed are computed in the kernels); an explicit `noise` is asked for
+    noise.exponential(r, None, (B*T, n_class)) and noise.uniform(r, (B*T, )).
+    init = (src_lists, keep) as in sample_tokens.  round_hook(r, x_t, out, tokens, conf, scores) is called after round
+    r = 1 .. R and may overwrite x_t / out in place (teacher forcing); rounds after the last masked row of the whole
+    batch are not evaluated (their draws are still counted).  Returns int64 [n_books, B*T] (-1 off-texture)."""
+    P, nm = net.P, net.name
+    B, T = segm_tok.shape
+    dev = segm_tok.device
+    R = int(rounds)
+    if R < 1:
+        raise ValueError(f'rounds must be >= 1, got {rounds}')
+    if not float(choice_temp) >= 0.0:
+        raise ValueError(f'choice_temp must be >= 0, got {choice_temp}')
+    split = bool(getattr(net, 'split', False))
+    if split:
+        ops.split_overflow(reset=True)  # a flag left by an earlier stage is not this run's
+        if getattr(net, 'x8', False):
+            net.ensure_x8()  # calibration (an evaluation of its own) before the first round, never inside one
+            ops.split_overflow(reset=True)
+    noise = noise or TorchDeviceNoise(dev)
+    n = B * T
+    n_class = P[f'{nm}.heads'].shape[1]
+    tex_flat = tex_tok.reshape(-1).contiguous()
+    tex_host = tex_flat.cpu().numpy()
+    if tex_host.size and (int(tex_host.min()) < 0 or int(tex_host.max()) >= n_books):
+        raise _lib.T2HError(f'texture ids must lie in [0, {n_books}), got [{int(tex_host.min())}, {int(tex_host.max())}]')
+    m0 = np.full(B, T, dtype=np.int64)
+    if init is not None:
+        src_lists, keep = init
+        if tuple(src_lists.shape) != (n_books, n) or tuple(keep.shape) != (n, ):
+            raise ValueError(f'init: source lists [{n_books}, {n}] and keep [{n}] expected, got '
+                             f'{tuple(src_lists.shape)} / {tuple(keep.shape)}')
+        x_t = torch.empty((B, T), dtype=torch.int64, device=dev)
+        out = torch.empty((n_books, n), dtype=torch.int64, device=dev)
+        err = ops.edit_prefill(src_lists, tex_flat, keep, mask_id, n_class, x_t=x_t, out=out)
+        kept = _init_check(err, keep, T)  # (raises before the generator has moved)
+        m0 = T - kept.reshape(B, T).sum(1).astype(np.int64)
+    else:
+        x_t = torch.full((B, T), mask_id, dtype=torch.int64, device=dev)
+        out = torch.full((n_books, n), -1, dtype=torch.int64, device=dev)
+    # the run's tables [R][w]: rows channel = k_r of every sample, 64-bit channel = generator offsets of the round's
+    # exponential_ / rand draws, 32-bit channel = the bits of tau_r
+    w = max(B, 2)
+    k_tbl = np.zeros((R, w), dtype=np.int32)
+    for b in range(B):
+        k_tbl[:, b] = schedule.confidence_schedule(int(m0[b]), R)[1]
+    tau_tbl = np.zeros((R, w), dtype=np.float32)
+    tau_tbl[:, 0] = schedule.confidence_choice_temps(R, choice_temp)
+    off_tbl = np.zeros((R, w), dtype=np.int64)
+    philox = isinstance(noise, TorchDeviceNoise) and noise.emulation_ok(n, n_class)
+    seed = None
+    if philox:
+        gen, _ = noise.generator()
+        seed, off0 = gen.initial_seed(), gen.get_offset()
+        _, rand_inc = ops.torch_draw_geometry(n, dev)
+        _, expo_inc = ops.torch_draw_geometry(n * n_class, dev)
+        off_tbl[:, 0] = off0 + np.arange(R, dtype=np.int64) * (expo_inc + rand_inc)
+        off_tbl[:, 1] = off_tbl[:, 0] + expo_inc
+        gen.set_offset(off0 + R * (expo_inc + rand_inc))  # where the 2 R torch draws would leave it
+    live = np.nonzero(k_tbl.sum(1))[0]
+    n_eval = int(live[-1]) + 1 if live.size else 0
+    net.last_stats = dict(mode='confidence', rounds=R, steps=R, batch=int(B), sample_steps_possible=int(B * R),
+                          sample_steps_needed=int((k_tbl[:, :B] > 0).sum()), sample_steps_launched=int(B * n_eval),
+                          rows_kept=int(n - m0.sum()))
+    net.last_launch_mode = 'eager'
+    k_dev, off_dev = torch.from_numpy(k_tbl).to(dev), torch.from_numpy(off_tbl).to(dev)
+    tau_dev = torch.from_numpy(tau_tbl.view(np.int32)).to(dev)
+    ctr = torch.zeros(1, dtype=torch.int32, device=dev)
+    cur_k, cur_off, cur_tau = (torch.zeros(w, dtype=torch.int32, device=dev), torch.zeros(w, dtype=torch.int64, device=dev),
+                               torch.zeros(w, dtype=torch.int32, device=dev))
+    tok = torch.empty(n, dtype=torch.int32, device=dev)
+    conf = torch.empty(n, dtype=torch.float32, device=dev)
+    scores = torch.empty(n, dtype=torch.float32, device=dev)
+    group_ws = ops.confidence_group_ws(n, n_books, dev)
+    logits_ws = torch.empty((n, n_class), dtype=torch.float32, device=dev)
+    lnf_g, lnf_b, heads = P[f'{nm}.ln_f.g'], P[f'{nm}.ln_f.b'], P[f'{nm}.heads']
+    for r in range(1, n_eval + 1):
+        ops.schedule_advance(k_dev, off_dev, tau_dev, ctr, cur_k, cur_off, cur_tau, w)
+        if philox:
+            noise_e, noise_u = ('philox', seed, cur_off[0:1]), ('philox', seed, cur_off[1:2])
+        else:
+            noise_e = ('explicit', noise.exponential(r, None, (n, n_class)).to(dev, torch.float32).contiguous())
+            noise_u = ('explicit', noise.uniform(r, (n, )).to(dev, torch.float32).reshape(-1).contiguous())
+        hidden = net.hidden(x_t, segm_tok, tex_tok)
+        ops.confidence_tail(hidden, lnf_g, lnf_b, heads, tex_flat, x_t.view(-1), mask_id, temp, noise_e, tok, conf,
+                            group_ws=group_ws, logits_ws=logits_ws)
+        ops.confidence_commit(conf, tok, tex_flat, noise_u, cur_k, cur_tau.view(torch.float32), mask_id, x_t, out,
+                              n_class, scores=scores)
+        if round_hook is not None:
+            round_hook(r, x_t, out, tok, conf, scores)
+    if not philox:  # the draws of the rounds that were not evaluated
+        for r in range(n_eval + 1, R + 1):
+            noise.exponential(r, None, (n, n_class))
+            noise.uniform(r, (n, ))
+    if split:
+        check_split_overflow('index sampler')
+    return out
+
+
 # ---------------------------------------------------------------- UNet + heads
 
 

@@ -14,7 +14,7 @@ import os
 import numpy as np
 import torch
 
-from .. import _lib, engine, ops, weights
+from .. import _lib, engine, ops, options, weights
 from ..ops import ACT_RELU
 
 logger = logging.getLogger('base')
@@ -111,8 +111,19 @@ class BaseSampleModel():
         """models/sample_model.py:256-328 -> list of 18 int64 [B, 512]."""
         return self._sample(temp, sample_steps or self.sample_steps)
 
-    def _sample(self, temp, sample_steps, init=None):
-        """sample_fn's body (init: engine.sample_tokens' initial state of a region edit)."""
+    @torch.no_grad()
+    def sample_fn_confidence(self, rounds=16, temp=1.0, choice_temp=4.5):
+        """Confidence-ordered parallel decoding (opt-in; DESIGN.md "Confidence-ordered decoding"): all tokens in
+        `rounds` transformer evaluations instead of one per active step -> list of 18 int64 [B, 512] like sample_fn."""
+        return self._sample(temp, None, confidence=(int(rounds), float(choice_temp)))
+
+    def _confidence_options(self):
+        """(rounds, choice_temp) if the options select `sample_order: confidence`, else None (the reference's loop)."""
+        return options.sampling_order(self.opt)
+
+    def _sample(self, temp, sample_steps, init=None, confidence=None):
+        """sample_fn's body (init: engine.sample_tokens' initial state of a region edit; confidence = (rounds,
+        choice_temp): engine.sample_tokens_confidence instead of the reference's loop)."""
         tex_tok = self._texture_tokens(self.texture_mask)
         # The reference computes ANY checkpoint in fp32 (transformer_arch.py:91-99).  The split-precision kernels
         # cover |x| < 65504; an activation outside raises SplitOverflowError at the end of the run -- after
@@ -125,8 +136,13 @@ class BaseSampleModel():
         try:
             for _ in range(3):  # x8 planes -> fp16 planes -> exact fp32, each at most once
                 try:
-                    out = engine.sample_tokens(net, self.segm_tokens.contiguous(), tex_tok, sample_steps, self.mask_id,
-                                               temp=temp, noise=self.noise, init=init)
+                    if confidence is not None:
+                        out = engine.sample_tokens_confidence(net, self.segm_tokens.contiguous(), tex_tok, self.mask_id,
+                                                              rounds=confidence[0], temp=temp,
+                                                              choice_temp=confidence[1], noise=self.noise, init=init)
+                    else:
+                        out = engine.sample_tokens(net, self.segm_tokens.contiguous(), tex_tok, sample_steps,
+                                                   self.mask_id, temp=temp, noise=self.noise, init=init)
                     break
                 except engine.X8RangeError as e:
                     # an activation beyond 14x its calibration maximum: the 8-bit planes saturated, the fp16 planes are
@@ -185,17 +201,22 @@ class BaseSampleModel():
         return ops.region_keep(b, hh, ww, (th, tw), parsing=segm, labels=[int(x) for x in labels])
 
     @torch.no_grad()
-    def resample_fn(self, top_indices_list, keep, temp=1.0, sample_steps=None):
+    def resample_fn(self, top_indices_list, keep, temp=1.0, sample_steps=None, order='random', rounds=None,
+                    choice_temp=4.5):
         """sample_fn started from `top_indices_list` (18 x int64 [B, 512], e.g. an earlier sample_fn result or a photo's
         top_encode indices) with the rows where keep [B, 512] is nonzero kept.  -> list of 18 int64 [B, 512] in
         sample_fn's format.  A kept row must have an index under the CURRENT texture map (T2HError otherwise; nothing
-        changes)."""
+        changes).  order='confidence': the masked rows are filled by confidence-ordered decoding in `rounds` (default
+        16) rounds, every sample on the schedule of its own number of resampled rows."""
+        if order not in ('random', 'confidence'):
+            raise ValueError(f"order must be 'random' or 'confidence', got {order!r}")
         init = (self._token_lists(top_indices_list, 'resample_fn'), self._keep_rows(keep))
-        return self._sample(temp, sample_steps or self.sample_steps, init=init)
+        confidence = (int(rounds or 16), float(choice_temp)) if order == 'confidence' else None
+        return self._sample(temp, sample_steps or self.sample_steps, init=init, confidence=confidence)
 
     @torch.no_grad()
     def edit_and_refine(self, top_indices_list, region=None, labels=None, bot_indices_list=None, save_dir=None,
-                        img_name=None):
+                        img_name=None, order='random', rounds=None, choice_temp=4.5):
         """Region edit end to end: resample the top tokens of the region (region_keep), predict the bottom indices,
         keep `bot_indices_list` (e.g. a photo's bot_encode) outside the region if given, decode.  Return values and
         files follow sample_and_refine: with save_dir and img_name both None the first image f32 [1, 3, H, W];
@@ -209,7 +230,7 @@ class BaseSampleModel():
             tex = self._texture_tokens(self.texture_mask).reshape(-1)
             err = ops.edit_prefill(bot, tex, keep_rows, 0, self.P['bot.books'].shape[1])  # (check only)
             engine._init_check(err, keep_rows, self.shape[0] * self.shape[1])
-        top = self.resample_fn(top_indices_list, keep)
+        top = self.resample_fn(top_indices_list, keep, order=order, rounds=rounds, choice_temp=choice_temp)
         want_files = not (save_dir is None and img_name is None)
         bot_keep = (bot, keep_rows) if bot is not None else None
         if not want_files:
@@ -336,7 +357,11 @@ class BaseSampleModel():
         """models/sample_model.py:215-254.  With both arguments None returns the
         first sample as f32 [1,3,512,256] in [0,1] (what ui_demo.py:162 uses);
         otherwise writes {save_dir}/{img_name[i]} PNGs."""
-        sampled_top_indices_list = self.sample_fn(temp=1, sample_steps=self.sample_steps)
+        confidence = self._confidence_options()
+        if confidence is not None:  # (options: sample_order: confidence)
+            sampled_top_indices_list = self.sample_fn_confidence(rounds=confidence[0], temp=1, choice_temp=confidence[1])
+        else:
+            sampled_top_indices_list = self.sample_fn(temp=1, sample_steps=self.sample_steps)
         want_files = not (save_dir is None and img_name is None)
         if not want_files:
             keep_b, keep_mask = self.batch_size, self.texture_mask

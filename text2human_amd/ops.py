@@ -929,6 +929,86 @@ def sample_heads(hidden, lnf_g, lnf_b, w_heads, expo_by_head, rows, n_rows, tex,
     check(_lib.load().t2h_sample_heads(ctypes.byref(a), _stream()), 't2h_sample_heads')
 
 
+def confidence_group_ws(n, n_heads, device):
+    """Workspace of confidence_tail's grouping launch (int32)."""
+    return torch.empty(int(_lib.load().t2h_confidence_group_ws_ints(int(n), int(n_heads))), dtype=torch.int32,
+                       device=device)
+
+
+def _philox_fields(a, noise, numel, device):
+    """noise = ('philox', seed, offset): ints, or int64 device tensors (values a replayed round reads from memory)."""
+    _, seed, off = noise
+    for name, v in (('philox_seed', seed), ('philox_offset', off)):
+        if torch.is_tensor(v):
+            assert v.dtype == torch.int64 and v.is_cuda and v.numel() >= 1
+            setattr(a, name + '_dev', v.data_ptr())
+        else:
+            setattr(a, name, int(v) & 0xFFFFFFFFFFFFFFFF)
+    a.philox_grid_threads = torch_draw_geometry(numel, device)[0]
+
+
+def confidence_tail(hidden, lnf_g, lnf_b, w_heads, tex, x_t, mask_id, temp, noise, tok, conf, group_ws=None,
+                    logits_ws=None):
+    """Token and confidence of EVERY masked row (t2h_confidence_tail): hidden f32 [n, C], w_heads [n_heads, n_class, C],
+    tex / x_t int64 [n] -> tok int32 [n] (-1 where not masked), conf f32 [n] (-inf where not masked).  noise:
+    ('explicit', E f32 [n, n_class]) or ('philox', seed, offset) = the elements of torch's
+    `empty(n, n_class).exponential_()` at that generator state."""
+    _chk_f32(hidden, lnf_g, lnf_b, w_heads, conf)
+    _chk_i64(tex, x_t)
+    n, C = hidden.shape
+    n_heads, n_class = w_heads.shape[0], w_heads.shape[1]
+    assert hidden.is_contiguous() and w_heads.is_contiguous() and tex.numel() == n and x_t.numel() == n
+    assert tok.dtype == torch.int32 and tok.is_cuda and tok.numel() == n and conf.numel() == n
+    dev = hidden.device
+    group_ws = group_ws if group_ws is not None else confidence_group_ws(n, n_heads, dev)
+    logits_ws = logits_ws if logits_ws is not None else torch.empty((n, n_class), dtype=torch.float32, device=dev)
+    assert group_ws.dtype == torch.int32 and logits_ws.dtype == torch.float32 and logits_ws.numel() >= n * n_class
+    assert group_ws.numel() >= int(_lib.load().t2h_confidence_group_ws_ints(n, n_heads))
+    a = _lib.ConfidenceTailArgs()
+    a.hidden, a.lnf_gamma, a.lnf_beta, a.w_heads = hidden.data_ptr(), lnf_g.data_ptr(), lnf_b.data_ptr(), w_heads.data_ptr()
+    a.tex, a.x_t, a.mask_id, a.temp = tex.data_ptr(), x_t.data_ptr(), int(mask_id), float(temp)
+    a.n, a.C, a.n_class, a.n_heads = n, C, n_class, n_heads
+    if noise[0] == 'explicit':
+        e = noise[1]
+        _chk_f32(e)
+        assert e.is_contiguous() and e.numel() == n * n_class
+        a.expo = e.data_ptr()
+    else:
+        _philox_fields(a, noise, n * n_class, dev)
+    a.group_ws, a.logits_ws, a.tok, a.conf = group_ws.data_ptr(), logits_ws.data_ptr(), tok.data_ptr(), conf.data_ptr()
+    check(_lib.load().t2h_confidence_tail(ctypes.byref(a), _stream()), 't2h_confidence_tail')
+    return tok, conf
+
+
+def confidence_commit(conf, tok, tex, noise, k, tau, mask_id, x_t, out, n_class, scores=None):
+    """Commits, per sample, the k[b] masked rows with the largest score conf + tau * gumbel(U) (t2h_confidence_commit):
+    x_t int64 [B, T] and out int64 [n_heads, B * T] are updated in place.  k int32 [>= B] and tau f32 [>= 1] are device
+    tensors; noise: ('explicit', U f32 [B * T]) or ('philox', seed, offset) = the elements of torch's `rand(B * T)`."""
+    _chk_f32(conf, tau)
+    _chk_i64(tex, x_t, out)
+    B, T = x_t.shape
+    n = B * T
+    n_heads = out.shape[0]
+    assert tuple(out.shape) == (n_heads, n) and conf.numel() == n and tok.numel() == n and tex.numel() == n
+    assert tok.dtype == torch.int32 and k.dtype == torch.int32 and k.is_cuda and k.numel() >= B and tau.numel() >= 1
+    a = _lib.ConfidenceCommitArgs()
+    a.conf, a.tok, a.tex = conf.data_ptr(), tok.data_ptr(), tex.data_ptr()
+    if noise[0] == 'explicit':
+        u = noise[1]
+        _chk_f32(u)
+        assert u.is_contiguous() and u.numel() == n
+        a.u = u.data_ptr()
+    else:
+        _philox_fields(a, noise, n, x_t.device)
+    a.k, a.tau, a.mask_id, a.x_t, a.out = k.data_ptr(), tau.data_ptr(), int(mask_id), x_t.data_ptr(), out.data_ptr()
+    if scores is not None:
+        _chk_f32(scores)
+        assert scores.numel() == n
+        a.scores = scores.data_ptr()
+    a.B, a.T, a.n_heads, a.n_class = B, T, n_heads, int(n_class)
+    check(_lib.load().t2h_confidence_commit(ctypes.byref(a), _stream()), 't2h_confidence_commit')
+
+
 def sample_head(hidden, lnf_g, lnf_b, w_head, expo, changes, tex, head, temp, x_t, out_idx):
     _chk_f32(hidden, lnf_g, lnf_b, w_head, expo)
     n, C = hidden.shape

@@ -74,6 +74,28 @@ def parse(opt_path, is_train=False, root=None):
     return opt
 
 
+# Sampling order of the index sampler ("Confidence-ordered decoding").  Absent keys = the reference's loop.
+SAMPLE_ORDERS = ('random', 'confidence')
+CONFIDENCE_ROUNDS, CONFIDENCE_CHOICE_TEMP = 16, 4.5
+
+
+def sampling_order(opt):
+    """-> None for the reference's random-order loop (no `sample_order` key, or `random`), else
+    (rounds, choice_temp) of `sample_order: confidence` with `confidence_rounds` / `confidence_choice_temp`
+    (defaults 16 / 4.5).  Raises ValueError on an unknown order or values out of range."""
+    order = opt.get('sample_order')
+    if order is None or order == 'random':
+        return None
+    if order not in SAMPLE_ORDERS:
+        raise ValueError(f'sample_order must be one of {SAMPLE_ORDERS}, got {order!r}')
+    rounds, ct = opt.get('confidence_rounds'), opt.get('confidence_choice_temp')
+    rounds = CONFIDENCE_ROUNDS if rounds is None else int(rounds)
+    ct = CONFIDENCE_CHOICE_TEMP if ct is None else float(ct)
+    if rounds < 1 or not ct >= 0.0:
+        raise ValueError(f'confidence_rounds >= 1 and confidence_choice_temp >= 0 expected, got {rounds}, {ct}')
+    return rounds, ct
+
+
 def dict2str(opt, indent_level=1):
     msg = ''
     pad = ' ' * (indent_level * 2)

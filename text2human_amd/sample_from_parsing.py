@@ -96,11 +96,20 @@ def run(pose=False, argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('-opt', type=str, required=True, help='Path to option YAML file.')
     ap.add_argument('--batch-size', type=int, default=4)
+    ap.add_argument('--order', choices=options.SAMPLE_ORDERS, default=None,
+                    help='index sampler: the reference\'s random-order loop or confidence-ordered parallel decoding '
+                         '(overrides sample_order of the YAML)')
+    ap.add_argument('--rounds', type=int, default=None, help='rounds of --order confidence (overrides confidence_rounds)')
     args = ap.parse_args(argv)
     rank, world, local_rank = dist_env()
     dist = init_dist(rank, world, local_rank)
     try:
         opt, logger = _setup(args.opt, 'test', rank, world, dist)
+        if args.order is not None:
+            opt['sample_order'] = args.order
+        if args.rounds is not None:
+            opt['confidence_rounds'] = args.rounds
+        options.sampling_order(opt)  # (a bad value ends the run here, before the checkpoints are read)
         if pose:
             dataset = DeepFashionAttrPoseDataset(pose_dir=opt['pose_dir'], texture_ann_dir=opt['texture_ann_file'],
                                                  shape_ann_path=opt['shape_ann_path'])

@@ -168,6 +168,29 @@ class RoundTables:
         return self.n_rounds - (1 if first_eager and self.n_rounds else 0)
 
 
+def confidence_schedule(m0, rounds):
+    """Confidence-ordered decoding ("Confidence-ordered decoding"): rows still masked after every round of a
+    sample that starts with m0 masked rows.  m_r = floor(m0 cos(pi/2 r / R)) in float64, then forced to m_R = 0 and
+    m_r <= max(m_{r-1} - 1, 0): every round commits at least one row while any is masked.
+    -> (m int64 [R + 1] with m[0] = m0, k int64 [R] with k[r - 1] = m[r - 1] - m[r] = rows committed in round r)"""
+    m0, R = int(m0), int(rounds)
+    if R < 1 or m0 < 0:
+        raise ValueError(f'confidence_schedule: rounds >= 1 and m0 >= 0 expected, got {rounds}, {m0}')
+    m = np.zeros(R + 1, dtype=np.int64)
+    m[0] = m0
+    for r in range(1, R + 1):
+        v = 0 if r == R else int(np.floor(np.float64(m0) * np.cos(np.float64(np.pi) / 2 * (np.float64(r) / np.float64(R)))))
+        m[r] = min(v, max(int(m[r - 1]) - 1, 0))
+    return m, m[:-1] - m[1:]
+
+
+def confidence_choice_temps(rounds, choice_temp):
+    """tau_r = choice_temp (1 - r / R), r = 1 .. R (float64 on the host, rounded once to the fp32 the kernel reads)"""
+    R = int(rounds)
+    r = np.arange(1, R + 1, dtype=np.float64)
+    return (np.float64(choice_temp) * (1.0 - r / np.float64(R))).astype(np.float32)
+
+
 def stats(round_steps, steps, active=None, kept=None):
     """Evaluation counts for the bench line: (sample, step) pairs the reference evaluates, pairs that
     change a token (the ones whose logits are read), rounds launched, and the (sample, round) pairs the
