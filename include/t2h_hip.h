@@ -355,6 +355,10 @@ typedef struct t2h_sample_heads_args {
   const int32_t* rng_rows;         /* optional, with row_philox_offset: rng_rows[i] = the row of the reference's
                                       [n, n_class] exponential_ tensor whose elements rows[i] draws (a host that
                                       reorders the samples of a batch keeps every row's own noise); NULL = rows[i] */
+  /* truncated sampling (see t2h_truncation_threshold): only the classes with l_j >= theta enter the race; both 0 = off
+   * (the kernels without it) */
+  int32_t top_k;
+  uint32_t top_p_q;
 } t2h_sample_heads_args;
 /* max |x| as the bits of the fp32 maximum, atomicMax'ed into *out_bits (the caller zeroes it; uint order = float order
  * for non-negative values, so the result does not depend on the order of the updates): of an fp32 matrix, and of the
@@ -457,6 +461,8 @@ typedef struct t2h_confidence_tail_args {
   float* logits_ws;
   int32_t* tok;             /* [n] */
   float* conf;              /* [n] */
+  int32_t top_k;            /* truncated sampling as in t2h_sample_heads_args: changes tok only -- conf stays the */
+  uint32_t top_p_q;         /* log-probability of the drawn token under the FULL softmax */
 } t2h_confidence_tail_args;
 typedef struct t2h_confidence_commit_args {
   const float* conf;
@@ -478,6 +484,19 @@ typedef struct t2h_confidence_commit_args {
 int64_t t2h_confidence_group_ws_ints(int32_t n, int32_t n_heads);
 int t2h_confidence_tail(const t2h_confidence_tail_args* args, void* stream);
 int t2h_confidence_commit(const t2h_confidence_commit_args* args, void* stream);
+
+/* Truncated sampling ("Truncated sampling"): one threshold theta per row of temperature-scaled logits l.
+ *   top_k (0 or >= n_class: off): theta_k = the k-th largest value counted with multiplicity; l_j >= theta_k survives
+ *   (ties at the threshold all survive).
+ *   top_p_q = rint(top_p * 2^20) (0 or 2^20: off), on the survivors of top-k: m_j = floor(expf(l_j - max l) * 2^32) as
+ *   a 64-bit integer, S = sum of m over the survivors, G(v) = sum of m_i over survivors with l_i > v; class j survives
+ *   iff G(l_j) * 2^20 < top_p_q * S (64-bit integers; n_class <= 2048).  theta_p = the smallest surviving value.
+ *   theta = max(theta_k, theta_p); -0 and +0 are one value (reported as +0).
+ * t2h_truncation_threshold runs the selection of the sampling kernels by itself on logits [n_rows][n_class]: scope 0 =
+ * the workgroup form (t2h_sample_heads), scope 1 = the wave form (t2h_confidence_tail) -- the same device function;
+ * theta [n_rows] (-inf with both rules off), kept [n_rows] = number of surviving classes. */
+int t2h_truncation_threshold(const float* logits, int32_t n_rows, int32_t n_class, int32_t top_k, uint32_t top_p_q,
+                             int32_t scope, float* theta, int32_t* kept, void* stream);
 
 /* Sampler training-time forward (models/transformer_model.py:212-274, forward only).
  * q_sample: mask[b,i] = u[b,i] < t[b] / num_timesteps; x_t = mask ? mask_id : x0.

@@ -61,6 +61,7 @@ class SampleHeadsArgs(ctypes.Structure):
         ('philox_grid_threads', ctypes.c_uint32),
         ('row_philox_offset', c_vp), ('expo_rows', c_vp), ('expo_slot', c_vp), ('philox_seed_dev', c_vp),
         ('rng_rows', c_vp),
+        ('top_k', c_i32), ('top_p_q', ctypes.c_uint32),
     ]
 
 
@@ -72,6 +73,7 @@ class ConfidenceTailArgs(ctypes.Structure):
         ('expo', c_vp), ('philox_seed', ctypes.c_uint64), ('philox_offset', ctypes.c_uint64),
         ('philox_seed_dev', c_vp), ('philox_offset_dev', c_vp), ('philox_grid_threads', ctypes.c_uint32),
         ('group_ws', c_vp), ('logits_ws', c_vp), ('tok', c_vp), ('conf', c_vp),
+        ('top_k', c_i32), ('top_p_q', ctypes.c_uint32),
     ]
 
 
@@ -129,6 +131,7 @@ SIGNATURES = {
     't2h_confidence_group_ws_ints': (c_i64, [c_i32, c_i32]),
     't2h_confidence_tail': (ctypes.c_int, [ctypes.POINTER(ConfidenceTailArgs), c_vp]),
     't2h_confidence_commit': (ctypes.c_int, [ctypes.POINTER(ConfidenceCommitArgs), c_vp]),
+    't2h_truncation_threshold': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, ctypes.c_uint32, c_i32, c_vp, c_vp, c_vp]),
     't2h_absmax_f32': (ctypes.c_int, [c_vp, c_i32, c_i64, c_i32, c_vp, c_vp]),
     't2h_split_rows_absmax': (ctypes.c_int, [c_vp, c_i64, c_i32, c_vp, c_vp]),
     't2h_gather_rows': (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]),

@@ -47,17 +47,151 @@ __global__ void unmask_step_kernel(const float* __restrict__ rnd, float thresh,
   }
 }
 
+// ---- truncated sampling (top-k / top-p; DESIGN.md, "Truncated sampling").  Truncation is ONE threshold per row: class j
+// enters the race iff l_j >= theta.  theta comes from a most-significant-digit radix select over order-preserving
+// 32-bit keys of the row's temperature-scaled logits, 8 bits per pass: a count histogram (top-k: the smallest value
+// with fewer than k values above it) and a 64-bit INTEGER mass histogram (top-p: m_j = floor(expf(l_j - max) 2^32),
+// the smallest surviving value v with G(v) 2^20 < p_q S, G(v) = mass strictly above v, S = mass of the top-k
+// survivors).  Only integers are accumulated, so the kept set does not depend on the order of the LDS atomics nor on
+// how the values are spread over threads: the workgroup form (NT = 1024) and the wave form (NT = 64) are this one
+// function.
+constexpr int TR_BINS = 256;
+struct trunc_lds {
+  uint32_t cnt[TR_BINS];
+  unsigned long long mass[TR_BINS];
+  unsigned long long sel_mass;                // mass above the selected bin
+  uint32_t sel_digit, sel_above, sel_in_bin;  // the selected bin, the values above it, the values in it
+};
+__device__ __forceinline__ uint32_t trunc_key(float l) {  // a < b <=> key(a) < key(b); -0 and +0 are one value
+  uint32_t u = __builtin_bit_cast(uint32_t, l);
+  if (l == 0.f) u = 0;
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float trunc_unkey(uint32_t k) {
+  return __builtin_bit_cast(float, (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+__device__ __forceinline__ unsigned long long trunc_mass(float l, float mx) {
+  float e = expf(l - mx);  // the value the race evaluates, in [0, 1]
+  e = e >= 0.f ? e : 0.f;  // (NaN rows: no mass)
+  return (unsigned long long)((double)e * 4294967296.0);  // exact scaling, then floor
+}
+template <int NT>
+__device__ __forceinline__ void trunc_sync() {
+  if (NT == 64) {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // one wave: its own LDS traffic has landed
+  } else {
+    __syncthreads();
+  }
+}
+// -> key of theta (0: nothing is cut), *kept = number of surviving classes.  All NT threads call it; t = 0 .. NT - 1;
+// thread t owns lg[t], lg[t + NT], ...; top_k == 0 / p_q == 0: that rule is off (not both).
+template <int NT>
+__device__ __forceinline__ uint32_t trunc_select(const float* lg, int n_class, float mx, int top_k, uint32_t p_q,
+                                                 trunc_lds* L, int t, int* kept) {
+  for (int b = t; b < TR_BINS; b += NT) {
+    L->cnt[b] = 0;
+    L->mass[b] = 0;
+  }
+  trunc_sync<NT>();
+  uint32_t floor_key = 0;  // survivors so far: key >= floor_key
+  int n_kept = n_class;
+  for (int stage = 0; stage < 2; ++stage) {
+    const bool by_mass = stage == 1;
+    if (by_mass ? p_q == 0 : top_k == 0) continue;
+    uint32_t prefix = 0, above_c = 0, in_bin = 0;
+    unsigned long long above_m = 0, S = 0;
+    for (int shift = 24; shift >= 0; shift -= 8) {
+      for (int j = t; j < n_class; j += NT) {
+        const float l = lg[j];
+        const uint32_t key = trunc_key(l);
+        if (key < floor_key || (shift < 24 && (key >> (shift + 8)) != prefix)) continue;
+        const int d = (key >> shift) & (TR_BINS - 1);
+        __hip_atomic_fetch_add(&L->cnt[d], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (by_mass) __hip_atomic_fetch_add(&L->mass[d], trunc_mass(l, mx), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
+      trunc_sync<NT>();
+      if (t < 64) {  // the first wave: 4 bins per lane, sums of the bins above by a butterfly; leaves the bins zeroed
+        uint32_t c[4], tot_c = 0, suf_c = 0;
+        unsigned long long m[4], tot_m = 0, suf_m = 0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          c[b] = L->cnt[4 * t + b];
+          m[b] = L->mass[4 * t + b];
+          L->cnt[4 * t + b] = 0;
+          L->mass[4 * t + b] = 0;
+          tot_c += c[b];
+          tot_m += m[b];
+        }
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+          const uint32_t oc = __shfl_xor(tot_c, o, 64);
+          const unsigned long long om = __shfl_xor(tot_m, o, 64);
+          if (!(t & o)) {
+            suf_c += oc;
+            suf_m += om;
+          }
+          tot_c += oc;
+          tot_m += om;
+        }
+        if (shift == 24) S = tot_m;  // the first pass of a stage sees every survivor
+        // the smallest non-empty bin whose largest value still qualifies (the predicate is monotone in the value)
+        int cand = TR_BINS;
+        uint32_t ac = above_c + suf_c, cand_c = 0, cand_n = 0;
+        unsigned long long am = above_m + suf_m, cand_m = 0;
+#pragma unroll
+        for (int b = 3; b >= 0; --b) {
+          const bool ok = by_mass ? (am << 20) < (unsigned long long)p_q * S : ac < (uint32_t)top_k;
+          if (c[b] > 0 && ok) {
+            cand = 4 * t + b;
+            cand_c = ac;
+            cand_m = am;
+            cand_n = c[b];
+          }
+          ac += c[b];
+          am += m[b];
+        }
+        int first = cand;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) first = min(first, __shfl_xor(first, o, 64));
+        if (first == TR_BINS) {  // (only rows of NaNs / infinities without any mass: nothing to select, no fault)
+          first = TR_BINS - 1;
+          cand = t == 0 ? first : TR_BINS;
+          cand_c = above_c;
+          cand_m = above_m;
+          cand_n = 0;
+        }
+        if (cand == first) {
+          L->sel_digit = (uint32_t)first;
+          L->sel_above = cand_c;
+          L->sel_mass = cand_m;
+          L->sel_in_bin = cand_n;
+        }
+      }
+      trunc_sync<NT>();
+      prefix = (prefix << 8) | L->sel_digit;
+      above_c = L->sel_above;
+      above_m = L->sel_mass;
+      in_bin = L->sel_in_bin;
+    }
+    floor_key = prefix;
+    n_kept = (int)(above_c + in_bin);
+  }
+  *kept = n_kept;
+  return floor_key;
+}
+
 // One workgroup per token row; rows that are not (changed && of this head's
 // texture) exit at once.  LN_f -> 512->n_class head (wave-cooperative dot
 // products, coalesced weight rows) -> exponential-race argmax.
 constexpr int SH_THREADS = 1024;
 
-template <int C>
+template <int C, bool TRUNC = false>
 __device__ __forceinline__ void sample_row(float* lds, int row, const float* __restrict__ hidden,
                                            const float* __restrict__ g, const float* __restrict__ bta,
                                            const float* __restrict__ w, const float* __restrict__ expo, int head,
                                            float temp, int64_t* __restrict__ x_t,
-                                           int64_t* __restrict__ out_idx, int n_class) {
+                                           int64_t* __restrict__ out_idx, int n_class, int top_k = 0,
+                                           uint32_t top_p_q = 0) {
   constexpr int VPL = C / 256;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float* xr = hidden + (int64_t)row * C;
@@ -119,11 +253,18 @@ __device__ __forceinline__ void sample_row(float* lds, int row, const float* __r
   mx = red[0];
 #pragma unroll
   for (int k = 1; k < NW; ++k) mx = fmaxf(mx, red[k]);
+  float theta = -INFINITY;
+  if constexpr (TRUNC) {
+    __shared__ trunc_lds tr;
+    int kept;
+    theta = trunc_unkey(trunc_select<SH_THREADS>(lds, n_class, mx, top_k, top_p_q, &tr, tid, &kept));
+  }
   // argmax_j exp(l_j - max) / q_j  (first index wins ties)
   const float* er = expo + (int64_t)row * n_class;
   float best = -1.f;
   int best_j = 0x7fffffff;
   for (int j = tid; j < n_class; j += SH_THREADS) {
+    if (TRUNC && !(lds[j] >= theta)) continue;
     const float sc = expf(lds[j] - mx) / er[j];
     if (sc > best) {
       best = sc;
@@ -552,6 +693,7 @@ __global__ __launch_bounds__(SL_THREADS) void sample_logits_kernel(const t2h_sam
   }
 }
 
+template <bool TRUNC>
 __global__ __launch_bounds__(SH_THREADS) void sample_pick_kernel(const t2h_sample_heads_args a, const float* __restrict__ ws) {
   __shared__ float red[2 * (SH_THREADS / 64)];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -567,6 +709,12 @@ __global__ __launch_bounds__(SH_THREADS) void sample_pick_kernel(const t2h_sampl
   mx = red[0];
 #pragma unroll
   for (int k = 1; k < NW; ++k) mx = fmaxf(mx, red[k]);
+  float theta = -INFINITY;
+  if constexpr (TRUNC) {
+    __shared__ trunc_lds tr;
+    int kept;
+    theta = trunc_unkey(trunc_select<SH_THREADS>(lg, a.n_class, mx, a.top_k, a.top_p_q, &tr, tid, &kept));
+  }
   // noise of this row: explicit compact rows (expo_rows[expo_slot[slot]]), the head's explicit full
   // tensor, or computed -- at the row's own generator offset when the list mixes steps
   const float* er = a.expo_rows ? a.expo_rows + (int64_t)(a.expo_slot ? a.expo_slot[slot] : slot) * a.n_class
@@ -580,6 +728,7 @@ __global__ __launch_bounds__(SH_THREADS) void sample_pick_kernel(const t2h_sampl
   float best = -1.f;
   int best_j = 0x7fffffff;
   for (int j = tid; j < a.n_class; j += SH_THREADS) {
+    if (TRUNC && !(lg[j] >= theta)) continue;
     const float q = er ? er[j]
                        : torch_exponential_at(pseed, poff, a.philox_grid_threads,
                                               (uint64_t)rng_row * a.n_class + j);
@@ -619,15 +768,16 @@ __global__ __launch_bounds__(SH_THREADS) void sample_pick_kernel(const t2h_sampl
 
 // All heads in one launch: one workgroup per CHANGED token (compact list from
 // unmask_step), which picks the head / noise tensor of its own texture.
-template <int C>
+template <int C, bool TRUNC>
 __global__ __launch_bounds__(SH_THREADS) void sample_heads_kernel(const t2h_sample_heads_args a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int row = a.rows[blockIdx.x];
   const int head = (int)a.tex[row];
   const float* expo = a.expo[head];
   if (expo == nullptr) return;  // cannot happen: a head with changed tokens always drew its noise
-  sample_row<C>(lds, row, a.hidden, a.lnf_gamma, a.lnf_beta, a.w_heads + (int64_t)head * a.n_class * C, expo, head,
-                a.temp, a.x_t, a.out_idx + (int64_t)head * a.n, a.n_class);  // (full hidden only)
+  sample_row<C, TRUNC>(lds, row, a.hidden, a.lnf_gamma, a.lnf_beta, a.w_heads + (int64_t)head * a.n_class * C, expo,
+                       head, a.temp, a.x_t, a.out_idx + (int64_t)head * a.n, a.n_class, a.top_k,
+                       a.top_p_q);  // (full hidden only)
 }
 
 // ---- confidence-ordered parallel decoding ("Confidence-ordered decoding").  A round samples EVERY masked
@@ -757,6 +907,7 @@ __global__ __launch_bounds__(CT_THREADS) void conf_logits_kernel(const t2h_confi
 // One wave per row: max, the exponential race of sample_pick_kernel (same scores, lowest index of the maximum), the
 // sum of the same exponentials, and the log-probability of the drawn class.
 constexpr int CP_ROWS = 4;
+template <bool TRUNC>
 __global__ __launch_bounds__(64 * CP_ROWS) void conf_pick_kernel(const t2h_confidence_tail_args a) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * CP_ROWS + (threadIdx.x >> 6);
@@ -773,6 +924,12 @@ __global__ __launch_bounds__(64 * CP_ROWS) void conf_pick_kernel(const t2h_confi
   float mx = -INFINITY;
   for (int j = lane; j < a.n_class; j += 64) mx = fmaxf(mx, lg[j]);
   mx = wave_max(mx);
+  float theta = -INFINITY;
+  if constexpr (TRUNC) {  // only the token changes: se / conf below stay those of the full softmax
+    __shared__ trunc_lds tr[CP_ROWS];
+    int kept;
+    theta = trunc_unkey(trunc_select<64>(lg, a.n_class, mx, a.top_k, a.top_p_q, &tr[threadIdx.x >> 6], lane, &kept));
+  }
   const float* er = a.expo ? a.expo + (int64_t)row * a.n_class : nullptr;
   const uint64_t pseed = a.philox_seed_dev ? *a.philox_seed_dev : a.philox_seed;
   const uint64_t poff = a.philox_offset_dev ? *a.philox_offset_dev : a.philox_offset;
@@ -783,6 +940,7 @@ __global__ __launch_bounds__(64 * CP_ROWS) void conf_pick_kernel(const t2h_confi
     const float ex = expf(lg[j] - mx);
     const float sc = ex / q;
     se += ex;
+    if (TRUNC && !(lg[j] >= theta)) continue;
     if (sc > best) {
       best = sc;
       best_j = j;
@@ -850,7 +1008,67 @@ __global__ __launch_bounds__(CC_THREADS) void conf_commit_kernel(const t2h_confi
   }
 }
 
+// ---- t2h_truncation_threshold: the selection alone, at the scope of sample_pick_kernel (one workgroup per row) or of
+// conf_pick_kernel (one wave per row); the row maximum is formed as those kernels form it.
+template <int NT>
+__global__ __launch_bounds__(NT == 64 ? 64 * CP_ROWS : SH_THREADS) void trunc_threshold_kernel(
+    const float* __restrict__ logits, int n_rows, int n_class, int top_k, uint32_t top_p_q, float* __restrict__ theta,
+    int* __restrict__ kept) {
+  constexpr int ROWS = NT == 64 ? CP_ROWS : 1, NW = NT / 64;
+  __shared__ trunc_lds tr[ROWS];
+  __shared__ float red[SH_THREADS / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int row = NT == 64 ? blockIdx.x * CP_ROWS + wave : blockIdx.x;
+  if (row >= n_rows) return;  // (uniform over the wave; the workgroup form has one row per workgroup)
+  const int t = NT == 64 ? lane : (int)threadIdx.x;
+  const float* lg = logits + (int64_t)row * n_class;
+  float mx = -INFINITY;
+  for (int j = t; j < n_class; j += NT) mx = fmaxf(mx, lg[j]);
+  mx = wave_max(mx);
+  if (NT != 64) {
+    if (lane == 0) red[wave] = mx;
+    __syncthreads();
+    mx = red[0];
+#pragma unroll
+    for (int k = 1; k < NW; ++k) mx = fmaxf(mx, red[k]);
+  }
+  int n_kept = n_class;
+  uint32_t key = 0;
+  if (top_k != 0 || top_p_q != 0) key = trunc_select<NT>(lg, n_class, mx, top_k, top_p_q, &tr[NT == 64 ? wave : 0], t, &n_kept);
+  if (t == 0) {
+    theta[row] = (top_k != 0 || top_p_q != 0) ? trunc_unkey(key) : -INFINITY;
+    kept[row] = n_kept;
+  }
+}
 }  // namespace
+
+// top_k >= n_class and top_p_q == 2^20 cut nothing: off (the existing kernels)
+static inline bool trunc_settings(int32_t n_class, int32_t* top_k, uint32_t* top_p_q) {
+  if (*top_k >= n_class) *top_k = 0;
+  if (*top_p_q == (1u << 20)) *top_p_q = 0;
+  return *top_k != 0 || *top_p_q != 0;
+}
+#define T2H_TRUNC_REQUIRE(name, a_top_k, a_top_p_q, a_n_class)                                                         \
+  T2H_REQUIRE((a_top_k) >= 0 && (a_top_p_q) <= (1u << 20) && ((a_top_p_q) == 0 || (a_n_class) <= 2048),                \
+              name ": top_k=%d / top_p_q=%u out of range (top_k >= 0, top_p_q <= 2^20; top-p: n_class <= 2048)",     \
+              (int)(a_top_k), (unsigned)(a_top_p_q))
+
+extern "C" int t2h_truncation_threshold(const float* logits, int32_t n_rows, int32_t n_class, int32_t top_k,
+                                        uint32_t top_p_q, int32_t scope, float* theta, int32_t* kept, void* stream) {
+  T2H_REQUIRE(logits && theta && kept, "t2h_truncation_threshold: NULL pointer");
+  T2H_REQUIRE(n_rows > 0 && n_class > 0 && (scope == 0 || scope == 1), "t2h_truncation_threshold: bad arguments");
+  T2H_TRUNC_REQUIRE("t2h_truncation_threshold", top_k, top_p_q, n_class);
+  trunc_settings(n_class, &top_k, &top_p_q);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (scope == 0)
+    hipLaunchKernelGGL(trunc_threshold_kernel<SH_THREADS>, dim3(n_rows), dim3(SH_THREADS), 0, s, logits, n_rows, n_class,
+                       top_k, top_p_q, theta, kept);
+  else
+    hipLaunchKernelGGL(trunc_threshold_kernel<64>, dim3((n_rows + CP_ROWS - 1) / CP_ROWS), dim3(64 * CP_ROWS), 0, s,
+                       logits, n_rows, n_class, top_k, top_p_q, theta, kept);
+  T2H_CHECK_LAUNCH("t2h_truncation_threshold");
+  return T2H_OK;
+}
 
 extern "C" int64_t t2h_confidence_group_ws_ints(int32_t n, int32_t n_heads) {
   if (n <= 0 || n_heads <= 0) return 0;
@@ -859,7 +1077,7 @@ extern "C" int64_t t2h_confidence_group_ws_ints(int32_t n, int32_t n_heads) {
 
 extern "C" int t2h_confidence_tail(const t2h_confidence_tail_args* args, void* stream) {
   T2H_REQUIRE(args != nullptr, "t2h_confidence_tail: args is NULL");
-  const t2h_confidence_tail_args a = *args;
+  t2h_confidence_tail_args a = *args;
   T2H_REQUIRE(a.hidden && a.lnf_gamma && a.lnf_beta && a.w_heads && a.tex && a.x_t && a.group_ws && a.logits_ws &&
                   a.tok && a.conf,
               "t2h_confidence_tail: NULL pointer");
@@ -869,10 +1087,15 @@ extern "C" int t2h_confidence_tail(const t2h_confidence_tail_args* args, void* s
   T2H_REQUIRE(a.C == 512, "t2h_confidence_tail: C=%d unsupported (512)", a.C);
   T2H_REQUIRE(a.expo != nullptr || (a.philox_grid_threads != 0 && (a.philox_offset_dev || a.philox_offset % 4 == 0)),
               "t2h_confidence_tail: no noise (expo, or philox_grid_threads and an offset that is a multiple of 4)");
+  T2H_TRUNC_REQUIRE("t2h_confidence_tail", a.top_k, a.top_p_q, a.n_class);
+  const bool trunc = trunc_settings(a.n_class, &a.top_k, &a.top_p_q);
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(conf_group_kernel, dim3(1), dim3(1024), 0, s, a.x_t, a.tex, a.mask_id, a.n, a.n_heads, a.group_ws);
   hipLaunchKernelGGL(conf_logits_kernel<512>, dim3(conf_max_tiles(a.n, a.n_heads) * CT_SPLIT), dim3(CT_THREADS), 0, s, a);
-  hipLaunchKernelGGL(conf_pick_kernel, dim3((a.n + CP_ROWS - 1) / CP_ROWS), dim3(64 * CP_ROWS), 0, s, a);
+  if (trunc)
+    hipLaunchKernelGGL(conf_pick_kernel<true>, dim3((a.n + CP_ROWS - 1) / CP_ROWS), dim3(64 * CP_ROWS), 0, s, a);
+  else
+    hipLaunchKernelGGL(conf_pick_kernel<false>, dim3((a.n + CP_ROWS - 1) / CP_ROWS), dim3(64 * CP_ROWS), 0, s, a);
   T2H_CHECK_LAUNCH("t2h_confidence_tail");
   return T2H_OK;
 }
@@ -935,7 +1158,7 @@ extern "C" int t2h_sample_head(const float* hidden, const float* lnf_gamma, cons
 
 extern "C" int t2h_sample_heads(const t2h_sample_heads_args* args, void* stream) {
   T2H_REQUIRE(args != nullptr, "t2h_sample_heads: args is NULL");
-  const t2h_sample_heads_args a = *args;
+  t2h_sample_heads_args a = *args;
   T2H_REQUIRE(a.hidden && a.lnf_gamma && a.lnf_beta && a.w_heads && a.rows && a.tex && a.x_t && a.out_idx,
               "t2h_sample_heads: NULL pointer");
   T2H_REQUIRE(a.n > 0 && a.n_class > 0 && a.temp > 0.f && a.n_rows >= 0 && a.n_heads > 0 &&
@@ -949,17 +1172,26 @@ extern "C" int t2h_sample_heads(const t2h_sample_heads_args* args, void* stream)
                   ((a.expo_rows == nullptr && a.row_philox_offset == nullptr) || a.logits_ws != nullptr),
               "t2h_sample_heads: per-row noise (row_philox_offset / expo_rows) needs the two-launch form and, for "
               "offsets, philox_grid_threads");
+  T2H_TRUNC_REQUIRE("t2h_sample_heads", a.top_k, a.top_p_q, a.n_class);
+  const bool trunc = trunc_settings(a.n_class, &a.top_k, &a.top_p_q);
   if (a.n_rows == 0) return T2H_OK;
   if (a.logits_ws) {  // two launches, SL_SPLIT workgroups per row stream the head weights
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(sample_logits_kernel<512>, dim3(a.n_rows * SL_SPLIT), dim3(SL_THREADS), 0, s, a, a.logits_ws);
-    hipLaunchKernelGGL(sample_pick_kernel, dim3(a.n_rows), dim3(SH_THREADS), 0, s, a, a.logits_ws);
+    if (trunc)
+      hipLaunchKernelGGL(sample_pick_kernel<true>, dim3(a.n_rows), dim3(SH_THREADS), 0, s, a, a.logits_ws);
+    else
+      hipLaunchKernelGGL(sample_pick_kernel<false>, dim3(a.n_rows), dim3(SH_THREADS), 0, s, a, a.logits_ws);
     T2H_CHECK_LAUNCH("t2h_sample_heads");
     return T2H_OK;
   }
   const size_t lds = (size_t)(a.n_class + 2 * (SH_THREADS / 64)) * sizeof(float);
-  hipLaunchKernelGGL(sample_heads_kernel<512>, dim3(a.n_rows), dim3(SH_THREADS), lds,
-                     static_cast<hipStream_t>(stream), a);
+  if (trunc)
+    hipLaunchKernelGGL((sample_heads_kernel<512, true>), dim3(a.n_rows), dim3(SH_THREADS), lds,
+                       static_cast<hipStream_t>(stream), a);
+  else
+    hipLaunchKernelGGL((sample_heads_kernel<512, false>), dim3(a.n_rows), dim3(SH_THREADS), lds,
+                       static_cast<hipStream_t>(stream), a);
   T2H_CHECK_LAUNCH("t2h_sample_heads");
   return T2H_OK;
 }

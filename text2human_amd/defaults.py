@@ -134,6 +134,19 @@ def with_confidence_order(opt, rounds=16, choice_temp=4.5):
     return opt
 
 
+def with_truncation(opt, top_k=None, top_p=None):
+    """`opt` with the keys that make sample_and_refine / inference draw every token from the truncated distribution
+    (options.sampling_truncation; None leaves that rule off).  Returns opt."""
+    from . import options
+    options.truncation_settings(top_k, top_p)
+    for key, v in (('sample_top_k', top_k), ('sample_top_p', top_p)):
+        if v is None:
+            opt.pop(key, None)
+        else:
+            opt[key] = int(v) if key == 'sample_top_k' else float(v)
+    return opt
+
+
 def write_yaml(opt, path):
     with open(path, 'w') as f:
         yaml.safe_dump(dict(opt), f, sort_keys=False)

@@ -703,13 +703,14 @@ class RoundGraph:
     round -- a power of two --, temperature) for every count of running samples, before the first run
     (prepare), replayed for every round of every run."""
 
-    def __init__(self, net, B, T, steps, maxr, n_books, n_class, temp, mask_id, dev):
+    def __init__(self, net, B, T, steps, maxr, n_books, n_class, temp, mask_id, dev, trunc=(0, 0)):
         i64 = lambda *s: torch.empty(s, dtype=torch.int64, device=dev)
         i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)
         # (a weak reference: net._graphs owns this object -- a strong one would make a cycle that only the cyclic
         # collector frees, at a moment of ITS choosing, e.g. in the middle of another graph's capture)
         self._net = weakref.ref(net)
         self.maxr, self.temp, self.mask_id, self.n_class = maxr, float(temp), mask_id, n_class
+        self.trunc = _trunc_kw(trunc)  # (captured by value, like temp: part of the graph key)
         self.x_t, self.out, self.segm, self.tex = i64(B, T), i64(n_books, B * T), i64(B, T), i64(B, T)
         self.rows_tbl, self.offs_tbl, self.rng_tbl = i32(steps, maxr), i64(steps, maxr), i32(steps, maxr)
         self.cur_rows, self.cur_offs, self.cur_rng = i32(maxr), i64(maxr), i32(maxr)
@@ -747,7 +748,7 @@ class RoundGraph:
         ops.sample_heads(hidden, P[f'{nm}.ln_f.g'], P[f'{nm}.ln_f.b'], P[f'{nm}.heads'], {}, self.cur_rows, self.maxr,
                          self.tex.view(-1), self.temp, self.x_t, self.out,
                          row_noise=('philox', self.seed, self.cur_offs, self.cur_rng), hidden_compact=compact,
-                         logits_ws=self.logits_ws)
+                         logits_ws=self.logits_ws, **self.trunc)
 
     def capture(self, k):
         g = torch.cuda.CUDAGraph()
@@ -801,8 +802,20 @@ class RoundGraph:
         return self.out
 
 
+def _trunc_kw(trunc):
+    """validated (top_k, top_p_q) (ops.truncation_settings) -> the keyword arguments of the tail launches (p_q / 2^20 is
+    exact in floating point, so the launch recovers the same p_q)"""
+    k, p_q = trunc
+    return dict(top_k=int(k), top_p=(int(p_q) / ops.TOP_P_ONE if p_q else 1.0))
+
+
+def round_graph_key(B, T, sample_steps, maxr, temp, mask_id, n_books, x8, trunc=(0, 0)):
+    """What a captured round (RoundGraph) holds BY VALUE: two calls share a graph iff this key is equal."""
+    return (B, T, sample_steps, maxr, float(temp), int(mask_id), n_books, bool(x8), int(trunc[0]), int(trunc[1]))
+
+
 def sample_tokens(net, segm_tok, tex_tok, sample_steps, mask_id, temp=1.0, noise=None,
-                  n_books=18, step_hook=None, round_hook=None, compact=None, init=None):
+                  n_books=18, step_hook=None, round_hook=None, compact=None, init=None, top_k=None, top_p=None):
     """BaseSampleModel.sample_fn (models/sample_model.py:256-328) on device.
 
     The unmasking schedule and every generator offset are computed up front (build_schedule: they
@@ -816,6 +829,9 @@ def sample_tokens(net, segm_tok, tex_tok, sample_steps, mask_id, temp=1.0, noise
     tests/test_gpu_edge_cases.py).
     compact=False: one round per step that changes a token, all samples at that step.
     Returns int64 [18, B*T] (-1 off-texture).
+
+    top_k / top_p: truncated sampling ("Truncated sampling"; ops.truncation_settings): every token draw is
+    restricted to the classes at or above the row's threshold.  The generator is consumed as without it.
 
     init = (src_lists int64 [n_books, B*T], keep uint8 [B*T]) -- region editing ("Editing a region"): the
     rows with keep != 0 start as their source token and are never resampled; everything else is the loop above, with
@@ -837,6 +853,7 @@ def sample_tokens(net, segm_tok, tex_tok, sample_steps, mask_id, temp=1.0, noise
     noise = noise or TorchDeviceNoise(dev)
     n = B * T
     n_class = P[f'{nm}.heads'].shape[1]
+    trunc = ops.truncation_settings(top_k, top_p, n_class)  # (raises before the generator has moved)
     tex_flat = tex_tok.reshape(-1).contiguous()
     # finished samples leave the batch (T2H_SHRINK_BATCH=0 opts out; hooks see the batch in its own order)
     shrink = (compact and step_hook is None and round_hook is None and os.environ.get('T2H_SHRINK_BATCH', '1') != '0')
@@ -879,9 +896,10 @@ def sample_tokens(net, segm_tok, tex_tok, sample_steps, mask_id, temp=1.0, noise
         # padded rows per round: a power of two >= 16 (at most five graph sets per batch size, whatever the seeds)
         maxr = min(net.TRIM_MAX_ROWS, max(16, 1 << (int(sched.max_rows) - 1).bit_length()))
         net._buffers(n, net.desc['C'], dev)  # (a change of batch size drops the graphs of the old buffers)
-        key = (B, T, sample_steps, maxr, float(temp), int(mask_id), n_books, bool(getattr(net, 'x8', False)))
+        key = round_graph_key(B, T, sample_steps, maxr, temp, mask_id, n_books, getattr(net, 'x8', False), trunc)
         if key not in net._graphs:
-            net._graphs[key] = RoundGraph(net, B, T, sample_steps, maxr, n_books, n_class, temp, mask_id, dev)
+            net._graphs[key] = RoundGraph(net, B, T, sample_steps, maxr, n_books, n_class, temp, mask_id, dev,
+                                          trunc=trunc)
         return in_batch_order(net._graphs[key].run(sched, segm_tok, tex_tok, init=init).clone())
     if init is not None:
         x_t = torch.empty((B, T), dtype=torch.int64, device=dev)
@@ -902,7 +920,7 @@ def sample_tokens(net, segm_tok, tex_tok, sample_steps, mask_id, temp=1.0, noise
             hidden, hidden_compact = net.finish_tail(rows_r, hi - lo)
         ops.sample_heads(hidden, P[f'{nm}.ln_f.g'], P[f'{nm}.ln_f.b'], P[f'{nm}.heads'], {}, rows_r, hi - lo, tex_flat,
                          temp, x_t, out, row_noise=sched.row_noise(lo, hi), hidden_compact=hidden_compact,
-                         logits_ws=logits_ws)
+                         logits_ws=logits_ws, **_trunc_kw(trunc))
         if round_hook is not None:
             round_hook(r, sched.round_steps[r], x_t, out)
         if step_hook is not None:
@@ -913,7 +931,7 @@ def sample_tokens(net, segm_tok, tex_tok, sample_steps, mask_id, temp=1.0, noise
 
 
 def sample_tokens_confidence(net, segm_tok, tex_tok, mask_id, rounds=16, temp=1.0, choice_temp=4.5, noise=None,
-                             n_books=18, round_hook=None, init=None):
+                             n_books=18, round_hook=None, init=None, top_k=None, top_p=None):
     """Confidence-ordered parallel decoding ("Confidence-ordered decoding"; opt-in, sample_tokens is the
     reference's loop): `rounds` rounds, each ONE transformer evaluation of the whole batch, a token + confidence for
     every still-masked row (t2h_confidence_tail) and, per sample, the commit of the k_r rows with the largest score
@@ -923,7 +941,8 @@ def sample_tokens_confidence(net, segm_tok, tex_tok, mask_id, rounds=16, temp=1.
     reads nothing back.  Per round the device generator is consumed as `empty(B*T, n_class).exponential_()` then
     `rand(B*T)` would consume it (the elements needed are computed in the kernels); an explicit `noise` is asked for
     noise.exponential(r, None, (B*T, n_class)) and noise.uniform(r, (B*T, )).
-    init = (src_lists, keep) as in sample_tokens.  round_hook(r, x_t, out, tokens, conf, scores) is called after round
+    init = (src_lists, keep) as in sample_tokens.  top_k / top_p: truncated sampling as in sample_tokens -- it changes
+    the token a row draws, never its confidence (the log-probability under the full softmax).  round_hook(r, x_t, out, tokens, conf, scores) is called after round
     r = 1 .. R and may overwrite x_t / out in place (teacher forcing); rounds after the last masked row of the whole
     batch are not evaluated (their draws are still counted).  Returns int64 [n_books, B*T] (-1 off-texture)."""
     P, nm = net.P, net.name
@@ -943,6 +962,7 @@ def sample_tokens_confidence(net, segm_tok, tex_tok, mask_id, rounds=16, temp=1.
     noise = noise or TorchDeviceNoise(dev)
     n = B * T
     n_class = P[f'{nm}.heads'].shape[1]
+    trunc_kw = _trunc_kw(ops.truncation_settings(top_k, top_p, n_class))  # (raises before the generator has moved)
     tex_flat = tex_tok.reshape(-1).contiguous()
     tex_host = tex_flat.cpu().numpy()
     if tex_host.size and (int(tex_host.min()) < 0 or int(tex_host.max()) >= n_books):
@@ -1006,7 +1026,7 @@ def sample_tokens_confidence(net, segm_tok, tex_tok, mask_id, rounds=16, temp=1.
             noise_u = ('explicit', noise.uniform(r, (n, )).to(dev, torch.float32).reshape(-1).contiguous())
         hidden = net.hidden(x_t, segm_tok, tex_tok)
         ops.confidence_tail(hidden, lnf_g, lnf_b, heads, tex_flat, x_t.view(-1), mask_id, temp, noise_e, tok, conf,
-                            group_ws=group_ws, logits_ws=logits_ws)
+                            group_ws=group_ws, logits_ws=logits_ws, **trunc_kw)
         ops.confidence_commit(conf, tok, tex_flat, noise_u, cur_k, cur_tau.view(torch.float32), mask_id, x_t, out,
                               n_class, scores=scores)
         if round_hook is not None:

@@ -107,23 +107,31 @@ class BaseSampleModel():
 
     # ------------------------------------------------------------ stage S
     @torch.no_grad()
-    def sample_fn(self, temp=1.0, sample_steps=None):
-        """models/sample_model.py:256-328 -> list of 18 int64 [B, 512]."""
-        return self._sample(temp, sample_steps or self.sample_steps)
+    def sample_fn(self, temp=1.0, sample_steps=None, top_k=None, top_p=None):
+        """models/sample_model.py:256-328 -> list of 18 int64 [B, 512].  top_k / top_p (not in the reference; DESIGN.md
+        "Truncated sampling"): every draw only among the k most likely classes / the smallest set of most likely classes
+        holding top_p of the probability.  None = off = the reference's draw."""
+        return self._sample(temp, sample_steps or self.sample_steps, top_k=top_k, top_p=top_p)
 
     @torch.no_grad()
-    def sample_fn_confidence(self, rounds=16, temp=1.0, choice_temp=4.5):
+    def sample_fn_confidence(self, rounds=16, temp=1.0, choice_temp=4.5, top_k=None, top_p=None):
         """Confidence-ordered parallel decoding (opt-in; DESIGN.md "Confidence-ordered decoding"): all tokens in
         `rounds` transformer evaluations instead of one per active step -> list of 18 int64 [B, 512] like sample_fn."""
-        return self._sample(temp, None, confidence=(int(rounds), float(choice_temp)))
+        return self._sample(temp, None, confidence=(int(rounds), float(choice_temp)), top_k=top_k, top_p=top_p)
 
     def _confidence_options(self):
         """(rounds, choice_temp) if the options select `sample_order: confidence`, else None (the reference's loop)."""
         return options.sampling_order(self.opt)
 
-    def _sample(self, temp, sample_steps, init=None, confidence=None):
+    def _truncation_options(self):
+        """(top_k, top_p) of the options `sample_top_k` / `sample_top_p` (None, None: off)."""
+        return options.sampling_truncation(self.opt)
+
+    def _sample(self, temp, sample_steps, init=None, confidence=None, top_k=None, top_p=None):
         """sample_fn's body (init: engine.sample_tokens' initial state of a region edit; confidence = (rounds,
-        choice_temp): engine.sample_tokens_confidence instead of the reference's loop)."""
+        choice_temp): engine.sample_tokens_confidence instead of the reference's loop; top_k / top_p: truncated
+        sampling, passed to every attempt of the fall-back chain below)."""
+        ops.truncation_settings(top_k, top_p)  # (raises before anything is evaluated or drawn)
         tex_tok = self._texture_tokens(self.texture_mask)
         # The reference computes ANY checkpoint in fp32 (transformer_arch.py:91-99).  The split-precision kernels
         # cover |x| < 65504; an activation outside raises SplitOverflowError at the end of the run -- after
@@ -139,10 +147,12 @@ class BaseSampleModel():
                     if confidence is not None:
                         out = engine.sample_tokens_confidence(net, self.segm_tokens.contiguous(), tex_tok, self.mask_id,
                                                               rounds=confidence[0], temp=temp,
-                                                              choice_temp=confidence[1], noise=self.noise, init=init)
+                                                              choice_temp=confidence[1], noise=self.noise, init=init,
+                                                              top_k=top_k, top_p=top_p)
                     else:
                         out = engine.sample_tokens(net, self.segm_tokens.contiguous(), tex_tok, sample_steps,
-                                                   self.mask_id, temp=temp, noise=self.noise, init=init)
+                                                   self.mask_id, temp=temp, noise=self.noise, init=init,
+                                                   top_k=top_k, top_p=top_p)
                     break
                 except engine.X8RangeError as e:
                     # an activation beyond 14x its calibration maximum: the 8-bit planes saturated, the fp16 planes are
@@ -202,21 +212,23 @@ class BaseSampleModel():
 
     @torch.no_grad()
     def resample_fn(self, top_indices_list, keep, temp=1.0, sample_steps=None, order='random', rounds=None,
-                    choice_temp=4.5):
+                    choice_temp=4.5, top_k=None, top_p=None):
         """sample_fn started from `top_indices_list` (18 x int64 [B, 512], e.g. an earlier sample_fn result or a photo's
         top_encode indices) with the rows where keep [B, 512] is nonzero kept.  -> list of 18 int64 [B, 512] in
         sample_fn's format.  A kept row must have an index under the CURRENT texture map (T2HError otherwise; nothing
         changes).  order='confidence': the masked rows are filled by confidence-ordered decoding in `rounds` (default
-        16) rounds, every sample on the schedule of its own number of resampled rows."""
+        16) rounds, every sample on the schedule of its own number of resampled rows.  top_k / top_p: truncated
+        sampling of the resampled rows, as in sample_fn."""
         if order not in ('random', 'confidence'):
             raise ValueError(f"order must be 'random' or 'confidence', got {order!r}")
         init = (self._token_lists(top_indices_list, 'resample_fn'), self._keep_rows(keep))
         confidence = (int(rounds or 16), float(choice_temp)) if order == 'confidence' else None
-        return self._sample(temp, sample_steps or self.sample_steps, init=init, confidence=confidence)
+        return self._sample(temp, sample_steps or self.sample_steps, init=init, confidence=confidence, top_k=top_k,
+                            top_p=top_p)
 
     @torch.no_grad()
     def edit_and_refine(self, top_indices_list, region=None, labels=None, bot_indices_list=None, save_dir=None,
-                        img_name=None, order='random', rounds=None, choice_temp=4.5):
+                        img_name=None, order='random', rounds=None, choice_temp=4.5, top_k=None, top_p=None):
         """Region edit end to end: resample the top tokens of the region (region_keep), predict the bottom indices,
         keep `bot_indices_list` (e.g. a photo's bot_encode) outside the region if given, decode.  Return values and
         files follow sample_and_refine: with save_dir and img_name both None the first image f32 [1, 3, H, W];
@@ -230,7 +242,8 @@ class BaseSampleModel():
             tex = self._texture_tokens(self.texture_mask).reshape(-1)
             err = ops.edit_prefill(bot, tex, keep_rows, 0, self.P['bot.books'].shape[1])  # (check only)
             engine._init_check(err, keep_rows, self.shape[0] * self.shape[1])
-        top = self.resample_fn(top_indices_list, keep, order=order, rounds=rounds, choice_temp=choice_temp)
+        top = self.resample_fn(top_indices_list, keep, order=order, rounds=rounds, choice_temp=choice_temp,
+                               top_k=top_k, top_p=top_p)
         want_files = not (save_dir is None and img_name is None)
         bot_keep = (bot, keep_rows) if bot is not None else None
         if not want_files:
@@ -358,8 +371,13 @@ class BaseSampleModel():
         first sample as f32 [1,3,512,256] in [0,1] (what ui_demo.py:162 uses);
         otherwise writes {save_dir}/{img_name[i]} PNGs."""
         confidence = self._confidence_options()
+        top_k, top_p = self._truncation_options()  # (options: sample_top_k / sample_top_p)
+        trunc = {k: v for k, v in (('top_k', top_k), ('top_p', top_p)) if v is not None}
         if confidence is not None:  # (options: sample_order: confidence)
-            sampled_top_indices_list = self.sample_fn_confidence(rounds=confidence[0], temp=1, choice_temp=confidence[1])
+            sampled_top_indices_list = self.sample_fn_confidence(rounds=confidence[0], temp=1, choice_temp=confidence[1],
+                                                                 **trunc)
+        elif trunc:
+            sampled_top_indices_list = self.sample_fn(temp=1, sample_steps=self.sample_steps, **trunc)
         else:
             sampled_top_indices_list = self.sample_fn(temp=1, sample_steps=self.sample_steps)
         want_files = not (save_dir is None and img_name is None)

@@ -10,7 +10,7 @@ import os
 
 import torch
 
-from . import _lib
+from . import _lib, options
 from ._lib import GemmArgs, check
 
 ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2
@@ -866,8 +866,28 @@ def gather_rows(src, rows, n_rows, out=None):
     return out
 
 
+# (top_k, top_p) -> the validated (top_k, top_p_q) pair of the C structs: ONE helper, shared with the option surface
+TOP_P_ONE = options.TOP_P_ONE
+truncation_settings = options.truncation_settings
+
+
+def truncation_threshold(logits, top_k=None, top_p=None, scope=0):
+    """The row thresholds of truncated sampling by themselves (t2h_truncation_threshold): logits f32 [n_rows, n_class]
+    (already divided by the temperature) -> theta f32 [n_rows], kept int32 [n_rows].  scope 0 / 1: the workgroup /
+    wave form of the selection, as sample_heads / confidence_tail run it."""
+    _chk_f32(logits)
+    assert logits.dim() == 2 and logits.is_contiguous()
+    n_rows, n_class = logits.shape
+    k, p_q = truncation_settings(top_k, top_p, n_class)
+    theta = torch.empty(n_rows, dtype=torch.float32, device=logits.device)
+    kept = torch.empty(n_rows, dtype=torch.int32, device=logits.device)
+    check(_lib.load().t2h_truncation_threshold(_p(logits), n_rows, n_class, k, p_q, int(scope), _p(theta), _p(kept),
+                                               _stream()), 't2h_truncation_threshold')
+    return theta, kept
+
+
 def sample_heads(hidden, lnf_g, lnf_b, w_heads, expo_by_head, rows, n_rows, tex, temp, x_t, out_idx, split=True,
-                 philox=None, hidden_compact=False, row_noise=None, logits_ws=None):
+                 philox=None, hidden_compact=False, row_noise=None, logits_ws=None, top_k=0, top_p=1.0):
     """All heads in one launch: `rows` (int32, first n_rows valid) are the changed token
     rows, expo_by_head {head: [n, n_class] Exp(1) draw}, w_heads [n_heads, n_class, C],
     out_idx [n_heads, n].  philox = (seed, {head: generator offset}): the noise of the listed heads is
@@ -875,8 +895,10 @@ def sample_heads(hidden, lnf_g, lnf_b, w_heads, expo_by_head, rows, n_rows, tex,
     instead of being read from expo_by_head.  row_noise (row lists that mix sampling steps):
     ('philox', seed, offsets int64 [>= n_rows][, rng_rows int32 [>= n_rows]]) = per-listed-row generator offsets (and
     the rows of the reference's draw they belong to, if the samples were reordered), or
-    ('explicit', expo_rows f32 [*, n_class], slots int32 [>= n_rows]) = per-listed-row explicit draws."""
+    ('explicit', expo_rows f32 [*, n_class], slots int32 [>= n_rows]) = per-listed-row explicit draws.
+    top_k / top_p: truncated sampling (truncation_settings; the defaults are off = the kernels without it)."""
     _chk_f32(hidden, lnf_g, lnf_b, w_heads, *expo_by_head.values())
+    trunc = truncation_settings(top_k, top_p, w_heads.shape[1])
     if int(n_rows) == 0:
         return
     C = hidden.shape[1]
@@ -893,6 +915,7 @@ def sample_heads(hidden, lnf_g, lnf_b, w_heads, expo_by_head, rows, n_rows, tex,
     a.rows, a.tex, a.x_t, a.out_idx = rows.data_ptr(), tex.data_ptr(), x_t.data_ptr(), out_idx.data_ptr()
     a.temp, a.n_rows, a.n, a.C, a.n_class, a.n_heads = float(temp), int(n_rows), n, C, n_class, n_heads
     a.hidden_compact = int(bool(hidden_compact))
+    a.top_k, a.top_p_q = trunc
     if (split or philox is not None or hidden_compact or row_noise is not None) and n_rows > 0:
         # logits scratch: 8 workgroups per row share the weight stream
         ws = logits_ws if logits_ws is not None else torch.empty((int(n_rows), n_class), device=hidden.device,
@@ -948,11 +971,12 @@ def _philox_fields(a, noise, numel, device):
 
 
 def confidence_tail(hidden, lnf_g, lnf_b, w_heads, tex, x_t, mask_id, temp, noise, tok, conf, group_ws=None,
-                    logits_ws=None):
+                    logits_ws=None, top_k=0, top_p=1.0):
     """Token and confidence of EVERY masked row (t2h_confidence_tail): hidden f32 [n, C], w_heads [n_heads, n_class, C],
     tex / x_t int64 [n] -> tok int32 [n] (-1 where not masked), conf f32 [n] (-inf where not masked).  noise:
     ('explicit', E f32 [n, n_class]) or ('philox', seed, offset) = the elements of torch's
-    `empty(n, n_class).exponential_()` at that generator state."""
+    `empty(n, n_class).exponential_()` at that generator state.  top_k / top_p: truncated sampling
+    (truncation_settings) -- changes tok only, conf stays the log-probability under the full softmax."""
     _chk_f32(hidden, lnf_g, lnf_b, w_heads, conf)
     _chk_i64(tex, x_t)
     n, C = hidden.shape
@@ -968,6 +992,7 @@ def confidence_tail(hidden, lnf_g, lnf_b, w_heads, tex, x_t, mask_id, temp, nois
     a.hidden, a.lnf_gamma, a.lnf_beta, a.w_heads = hidden.data_ptr(), lnf_g.data_ptr(), lnf_b.data_ptr(), w_heads.data_ptr()
     a.tex, a.x_t, a.mask_id, a.temp = tex.data_ptr(), x_t.data_ptr(), int(mask_id), float(temp)
     a.n, a.C, a.n_class, a.n_heads = n, C, n_class, n_heads
+    a.top_k, a.top_p_q = truncation_settings(top_k, top_p, n_class)
     if noise[0] == 'explicit':
         e = noise[1]
         _chk_f32(e)

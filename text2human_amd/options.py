@@ -96,6 +96,44 @@ def sampling_order(opt):
     return rounds, ct
 
 
+# Truncated sampling ("Truncated sampling").  Absent keys = off = the reference's draw.
+TOP_P_ONE = 1 << 20  # top_p travels as rint(top_p * 2^20) (include/t2h_hip.h, t2h_truncation_threshold)
+
+
+def truncation_settings(top_k=None, top_p=None, n_class=None):
+    """(top_k, top_p) of the public surface -> the validated (top_k, top_p_q) pair of the C structs; (0, 0) = off.
+    top_k in {None, 0} or >= n_class is off, top_p in {None, 1.0} is off; valid are integers top_k >= 1 and
+    0 < top_p <= 1 (ValueError naming the value otherwise -- callers check before the generator moves)."""
+    import numbers
+    k = 0
+    if top_k is not None:
+        if isinstance(top_k, bool) or not isinstance(top_k, numbers.Integral) or int(top_k) < 0:
+            raise ValueError(f'top_k must be an integer >= 1 (None or 0: off), got {top_k!r}')
+        k = min(int(top_k), 0x7fffffff)
+        if n_class is not None and k >= int(n_class):
+            k = 0
+    p_q = 0
+    if top_p is not None:
+        if isinstance(top_p, bool) or not isinstance(top_p, numbers.Real):
+            raise ValueError(f'top_p must be a number in (0, 1] (None or 1.0: off), got {top_p!r}')
+        p = float(top_p)
+        if not 0.0 < p <= 1.0:
+            raise ValueError(f'top_p must lie in (0, 1] (None or 1.0: off), got {top_p!r}')
+        p_q = int(round(p * TOP_P_ONE))  # (round half to even, like rint)
+        if p_q == 0:
+            raise ValueError(f'top_p is too small (it is resolved in steps of 2^-20), got {top_p!r}')
+        if p_q == TOP_P_ONE:
+            p_q = 0
+    return k, p_q
+
+
+def sampling_truncation(opt):
+    """-> (top_k, top_p) of the options `sample_top_k` / `sample_top_p` (None where absent), validated."""
+    top_k, top_p = opt.get('sample_top_k'), opt.get('sample_top_p')
+    truncation_settings(top_k, top_p)
+    return top_k, top_p
+
+
 def dict2str(opt, indent_level=1):
     msg = ''
     pad = ' ' * (indent_level * 2)

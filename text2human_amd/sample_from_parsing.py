@@ -92,7 +92,7 @@ def _setup(opt_path, log_name, rank=0, world=1, dist=None):
     return opt, logger
 
 
-def run(pose=False, argv=None):
+def cli_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('-opt', type=str, required=True, help='Path to option YAML file.')
     ap.add_argument('--batch-size', type=int, default=4)
@@ -100,16 +100,33 @@ def run(pose=False, argv=None):
                     help='index sampler: the reference\'s random-order loop or confidence-ordered parallel decoding '
                          '(overrides sample_order of the YAML)')
     ap.add_argument('--rounds', type=int, default=None, help='rounds of --order confidence (overrides confidence_rounds)')
-    args = ap.parse_args(argv)
+    ap.add_argument('--top-k', type=int, default=None,
+                    help='index sampler: draw every token among its k most likely classes (overrides sample_top_k)')
+    ap.add_argument('--top-p', type=float, default=None,
+                    help='index sampler: draw every token from the most likely classes that hold this share of the '
+                         'probability (overrides sample_top_p)')
+    return ap
+
+
+def apply_cli(opt, args):
+    """The command line's overrides of the YAML's sampling keys, validated (a bad value ends the run here, before the
+    checkpoints are read).  Returns opt."""
+    for key, v in (('sample_order', args.order), ('confidence_rounds', args.rounds), ('sample_top_k', args.top_k),
+                   ('sample_top_p', args.top_p)):
+        if v is not None:
+            opt[key] = v
+    options.sampling_order(opt)
+    options.sampling_truncation(opt)
+    return opt
+
+
+def run(pose=False, argv=None):
+    args = cli_parser().parse_args(argv)
     rank, world, local_rank = dist_env()
     dist = init_dist(rank, world, local_rank)
     try:
         opt, logger = _setup(args.opt, 'test', rank, world, dist)
-        if args.order is not None:
-            opt['sample_order'] = args.order
-        if args.rounds is not None:
-            opt['confidence_rounds'] = args.rounds
-        options.sampling_order(opt)  # (a bad value ends the run here, before the checkpoints are read)
+        apply_cli(opt, args)
         if pose:
             dataset = DeepFashionAttrPoseDataset(pose_dir=opt['pose_dir'], texture_ann_dir=opt['texture_ann_file'],
                                                  shape_ann_path=opt['shape_ann_path'])
