@@ -4,6 +4,8 @@ import pytest
 
 from text2human_amd import schedule
 
+from schedule_util import check_plan  # noqa: E402
+
 
 def _random_schedule(B, T, steps, seed):
     """step of every token as the reference's loop would assign it (uniform thresholds 1/t)"""
@@ -163,26 +165,21 @@ def _reference_loop(step, tex, B, T, steps, mask_id):
 
 
 def _rounds_loop(step, tex, B, T, mask_id, shrink):
-    """engine.sample_tokens' host logic: (reordered) compact rounds; a round evaluates only the running prefix."""
-    perm = np.arange(B)
-    if shrink:
-        perm, _ = schedule.leave_order(step, B, T)
-    orig_row = (perm[:, None] * T + np.arange(T)[None, :]).reshape(-1)
-    step_p, tex_p = step[orig_row], tex[orig_row]
-    order, start, round_steps = schedule.group_rounds(step_p, B, T, compact=True)
-    active = (round_steps > 0).sum(1)
-    rng_rows = orig_row[order]
+    """The rounds engine.sample_tokens runs (schedule.plan_rounds: reordered if shrink, a round evaluates only the
+    running prefix), walked with the toy model."""
+    plan = schedule.plan_rounds(step, tex, B, T, True, shrink)
+    draw_rows = plan.rng_rows if plan.rng_rows is not None else plan.order   # the row of the reference's draw
     x = np.full((B, T), mask_id, dtype=np.int64)
-    for r in range(len(start) - 1):
-        lo, hi = int(start[r]), int(start[r + 1])
-        k = int(active[r]) if shrink else B
+    for r in range(len(plan.start) - 1):
+        lo, hi = int(plan.start[r]), int(plan.start[r + 1])
+        k = int(plan.active[r]) if shrink else B
         before = x.copy()                                   # the round's "hidden states": one evaluation, then writes
         for i in range(lo, hi):
-            row = int(order[i])
+            row, src = int(plan.order[i]), int(draw_rows[i])
             assert row // T < k
-            x[row // T, row % T] = _toy_token(before[row // T], row % T, int(rng_rows[i]), int(step_p[row]),
-                                              int(tex_p[row])) + 1024 * int(tex_p[row])
-    return x[np.argsort(perm)]                              # back in the caller's order (engine.in_batch_order)
+            x[row // T, row % T] = _toy_token(before[row // T], row % T, src, int(plan.round_steps[r, row // T]),
+                                              int(tex[src])) + 1024 * int(tex[src])
+    return x.reshape(-1)[schedule.in_caller_order(plan.perm, B, T)].reshape(B, T)   # back in the caller's order
 
 
 @pytest.mark.parametrize('B,T,steps,seed', [(4, 32, 16, 0), (7, 16, 40, 1), (3, 64, 256, 2), (1, 8, 3, 3)])
@@ -197,3 +194,18 @@ def test_compact_and_shrinking_rounds_give_the_reference_loops_tokens(B, T, step
     for shrink in (False, True):
         got = _rounds_loop(step, tex, B, T, 18432, shrink)
         assert (got == want).all(), f'shrink={shrink}'
+
+
+@pytest.mark.parametrize('B,T,steps,seed', [(4, 32, 16, 0), (7, 16, 40, 1), (1, 8, 3, 3)])
+def test_plan_rounds(B, T, steps, seed):
+    step = _random_schedule(B, T, steps, seed)
+    check_plan(step, np.random.default_rng(seed + 100).integers(0, 18, B * T), B, T, steps)
+
+
+def test_plan_rounds_keeps_a_batch_that_is_in_leave_order_already():
+    B, T = 3, 4
+    step = np.array([3, 2, 1, 1, 2, 2, 1, 1, 1, 1, 1, 1])   # 3, 2, 1 distinct steps: leave_order is the identity
+    plan = schedule.plan_rounds(step, np.zeros(B * T, dtype=np.int64), B, T, True, True)
+    assert plan.perm is None and plan.rng_rows is None and plan.active.tolist() == [3, 2, 1]
+    plan = schedule.plan_rounds(step[::-1].copy(), np.zeros(B * T, dtype=np.int64), B, T, True, True)
+    assert plan.perm.tolist() == [2, 1, 0] and plan.active.tolist() == [3, 2, 1]

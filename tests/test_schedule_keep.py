@@ -6,6 +6,8 @@ import pytest
 
 from text2human_amd import schedule
 
+from schedule_util import check_plan  # noqa: E402
+
 MASK_ID = 18432
 
 
@@ -132,26 +134,23 @@ def _reference_loop(step, tex, src, kept, B, T, steps):
 
 
 def _rounds_loop(step, tex, src, kept, B, T, compact, shrink):
-    """engine.sample_tokens' host logic with init: (reordered) rounds from the prefilled state"""
-    perm = np.arange(B)
-    if shrink:
-        perm, _ = schedule.leave_order(step, B, T, kept)
-    orig_row = (perm[:, None] * T + np.arange(T)[None, :]).reshape(-1)
-    step_p, tex_p, kept_p = step[orig_row], tex[orig_row], kept[orig_row]
-    order, start, round_steps = schedule.group_rounds(step_p, B, T, compact=compact, kept=kept_p)
-    active = (round_steps > 0).sum(1)
-    rng_rows = orig_row[order]
-    x = _initial_state(src[orig_row], tex_p, kept_p, B, T)   # the prefill, in the schedule's sample order
-    for r in range(len(start) - 1):
-        lo, hi = int(start[r]), int(start[r + 1])
-        k = int(active[r]) if shrink else B
+    """The rounds engine.sample_tokens runs with init (schedule.plan_rounds), walked with the toy model from the
+    prefilled state"""
+    plan = schedule.plan_rounds(step, tex, B, T, compact, shrink, kept)
+    draw_rows = plan.rng_rows if plan.rng_rows is not None else plan.order   # the row of the reference's draw
+    x = _initial_state(src, tex, kept, B, T)
+    if plan.perm is not None:
+        x = x[plan.perm]                                     # the prefill, in the schedule's sample order
+    for r in range(len(plan.start) - 1):
+        lo, hi = int(plan.start[r]), int(plan.start[r + 1])
+        k = int(plan.active[r]) if shrink else B
         before = x.copy()
         for i in range(lo, hi):
-            row = int(order[i])
-            assert row // T < k and not kept_p[row]
-            x[row // T, row % T] = _toy_token(before[row // T], int(rng_rows[i]), int(step_p[row]),
-                                              int(tex_p[row])) + 1024 * int(tex_p[row])
-    return x[np.argsort(perm)]
+            row, orig = int(plan.order[i]), int(draw_rows[i])
+            assert row // T < k and not plan.kept[row]
+            x[row // T, row % T] = _toy_token(before[row // T], orig, int(plan.round_steps[r, row // T]),
+                                              int(tex[orig])) + 1024 * int(tex[orig])
+    return x.reshape(-1)[schedule.in_caller_order(plan.perm, B, T)].reshape(B, T)
 
 
 @pytest.mark.parametrize('B,T,steps,density,seed', [(4, 32, 16, 0.5, 0), (7, 16, 40, 0.25, 1), (3, 64, 256, 0.75, 2),
@@ -167,3 +166,9 @@ def test_rounds_from_a_kept_state_give_the_restated_loops_tokens(B, T, steps, de
     for compact, shrink in ((True, False), (True, True), (False, False)):
         got = _rounds_loop(step, tex, src, kept, B, T, compact, shrink)
         assert (got == want).all(), (compact, shrink)
+
+
+@pytest.mark.parametrize('B,T,steps,density,seed', [(4, 32, 16, 0.5, 0), (7, 16, 40, 0.25, 1), (1, 8, 3, 0.5, 3)])
+def test_plan_rounds_with_kept_rows(B, T, steps, density, seed):
+    step, kept = _schedule_with_keep(B, T, steps, density, seed, full_kept=(B - 1, ) if B > 1 else ())
+    check_plan(step, np.random.default_rng(seed + 100).integers(0, 18, B * T), B, T, steps, kept)

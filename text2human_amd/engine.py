@@ -478,6 +478,10 @@ class SamplerNet:
             raise _lib.T2HError('x8 weight packing overflowed')  # (cannot happen: every scale is derived from its matrix's maximum)
         self._x8 = {'w': sw, 'a': sa, 'act_max': mx}
 
+    def final_norm_and_heads(self):
+        """(ln_f gamma, ln_f beta, heads [n_heads, n_class, C]): what every sampling tail reads after hidden()"""
+        return tuple(self.P[f'{self.name}.{k}'] for k in ('ln_f.g', 'ln_f.b', 'heads'))
+
     def logits(self, idx, segm_tok, tex_tok, heads=None):
         """Full [B*T, 1024] logits per head (tests / API parity only; the
         sampling loop never materialises them)."""
@@ -606,22 +610,31 @@ def _init_check(err, keep, T):
     return keep.cpu().numpy().astype(bool)
 
 
+def _texture_ids(tex_tok, n_books):
+    """(tex_flat int64 [B*T] on the device, its host copy -- the schedule needs it anyway), range-checked: the reference
+    raises on a bad id (transformer_arch.py:262, sample_model.py:300-317); here they would index device arrays"""
+    tex_flat = tex_tok.reshape(-1).contiguous()
+    tex_host = tex_flat.cpu().numpy()
+    if tex_host.size and (int(tex_host.min()) < 0 or int(tex_host.max()) >= n_books):
+        raise _lib.T2HError(f'texture ids must lie in [0, {n_books}), got [{int(tex_host.min())}, {int(tex_host.max())}]')
+    return tex_flat, tex_host
+
+
 def build_schedule(tex_tok, sample_steps, n_books, n_class, noise, compact=True, shrink=False, init=None):
     """The unmasking schedule + RNG bookkeeping of one sample_fn call (schedule.py), consuming
     `noise` exactly as the reference's loop would (models/sample_model.py:279-306).  shrink (compact rounds on the
     device generator only): the samples are reordered so that finished ones leave the batch (SampleSchedule.perm).
     init = (src_lists int64 [n_books, B*T], keep uint8 [B*T]) (region editing): the kept rows start unmasked and are
     never drawn; a kept row without a source token raises T2HError before the generator has moved."""
-    B, T = tex_tok.shape
-    dev = tex_tok.device
-    n = B * T
-    tex_flat = tex_tok.reshape(-1).contiguous()
-    tex_host = tex_flat.cpu().numpy()
-    # the reference indexes texture_emb / head_list with these ids and raises on a bad one
-    # (transformer_arch.py:262, sample_model.py:300-317); here they index device arrays -- checked on the
-    # host copy the schedule needs anyway (no extra device read)
-    if tex_host.size and (int(tex_host.min()) < 0 or int(tex_host.max()) >= n_books):
-        raise _lib.T2HError(f'texture ids must lie in [0, {n_books}), got [{int(tex_host.min())}, {int(tex_host.max())}]')
+    return _schedule(*_texture_ids(tex_tok, n_books), tex_tok.shape[0], sample_steps, n_books, n_class, noise, compact,
+                     shrink, init)
+
+
+def _schedule(tex_flat, tex_host, B, sample_steps, n_books, n_class, noise, compact, shrink, init):
+    """build_schedule on texture ids that were checked already (_texture_ids)"""
+    dev, n = tex_flat.device, tex_flat.numel()
+    T = n // B
+    to_dev = lambda a: torch.from_numpy(a).to(dev)
     keep = err = kept = None
     if init is not None:
         src_lists, keep = init
@@ -638,27 +651,10 @@ def build_schedule(tex_tok, sample_steps, n_books, n_class, noise, compact=True,
         head_mask = mask_dev.cpu().numpy().astype(np.int64) & 0xFFFFFFFF
         _, expo_off, final = schedule.draw_offsets(head_mask, sample_steps, off0, rand_inc, expo_inc, n_books)
         gen.set_offset(final)  # where the reference's generator stands after its loop
-        perm = rng_rows = rng_dev = active = None
-        if shrink and compact and B > 1:
-            perm, _ = schedule.leave_order(step_of_row, B, T, kept)
-            if (perm == np.arange(B)).all():
-                perm = None
-        if perm is not None:
-            orig_row = (perm[:, None] * T + np.arange(T)[None, :]).reshape(-1)  # original row of every reordered row
-            step_of_row, tex_host = step_of_row[orig_row], tex_host[orig_row]
-            kept = kept[orig_row] if kept is not None else None
-        order, start, round_steps = schedule.group_rounds(step_of_row, B, T, compact, kept)
-        offs = expo_off[step_of_row[order], tex_host[order]]
-        assert (offs >= 0).all()
-        if shrink and compact:
-            active = (round_steps > 0).sum(1).astype(np.int64)
-            assert all((round_steps[r, :active[r]] > 0).all() for r in range(len(active)))  # a prefix of the batch
-        if perm is not None:
-            rng_rows = orig_row[order].astype(np.int32)
-            rng_dev = torch.from_numpy(rng_rows).to(dev)
-        return SampleSchedule(torch.from_numpy(order.astype(np.int32)).to(dev), start, round_steps, 'philox', seed=seed,
-                              offsets=torch.from_numpy(offs).to(dev), host=(order, offs, rng_rows), perm=perm,
-                              rng_rows=rng_dev, active=active, kept=kept)
+        p = schedule.plan_rounds(step_of_row, tex_host, B, T, compact, shrink, kept, expo_off)
+        return SampleSchedule(to_dev(p.order.astype(np.int32)), p.start, p.round_steps, 'philox', seed=seed,
+                              offsets=to_dev(p.offs), host=(p.order, p.offs, p.rng_rows), perm=p.perm,
+                              rng_rows=None if p.rng_rows is None else to_dev(p.rng_rows), active=p.active, kept=p.kept)
     # explicit draws (tests replaying CPU noise; the emulation fallback): the reference's own loop
     # order, with the rows each head needs copied out of its full draw
     unmasked = torch.zeros(n, dtype=torch.uint8, device=dev)
@@ -684,14 +680,56 @@ def build_schedule(tex_tok, sample_steps, n_books, n_class, noise, compact=True,
         for h in np.nonzero(c[:n_books])[0]:  # ascending: the reference's draw order
             e = noise.exponential(t, int(h), (n, n_class)).to(dev, torch.float32).contiguous()
             rh = rows_t[tex_host[rows_t] == h]
-            ops.gather_rows(e, torch.from_numpy(rh.astype(np.int32)).to(dev), len(rh), out=expo_rows[fill:fill + len(rh)])
+            ops.gather_rows(e, to_dev(rh.astype(np.int32)), len(rh), out=expo_rows[fill:fill + len(rh)])
             slot_of_row[rh] = np.arange(fill, fill + len(rh), dtype=np.int32)
             fill += len(rh)
     n_kept = int(kept.sum()) if kept is not None else 0
     assert fill == n - n_kept, (fill, n, n_kept)
-    order, start, round_steps = schedule.group_rounds(step_of_row, B, T, compact, kept)
-    return SampleSchedule(torch.from_numpy(order.astype(np.int32)).to(dev), start, round_steps, 'explicit',
-                          expo_rows=expo_rows, slots=torch.from_numpy(slot_of_row[order]).to(dev), kept=kept)
+    p = schedule.plan_rounds(step_of_row, tex_host, B, T, compact, False, kept)
+    return SampleSchedule(to_dev(p.order.astype(np.int32)), p.start, p.round_steps, 'explicit', expo_rows=expo_rows,
+                          slots=to_dev(slot_of_row[p.order]), kept=kept)
+
+
+def _begin_run(net, tex_tok, n_books, noise, init, top_k, top_p):
+    """What both sampling loops do first -> (noise, n_class, trunc, tex_flat, tex_host); whatever raises here raises before
+    the generator has moved."""
+    if net.split:
+        ops.split_overflow(reset=True)  # a flag left by an earlier stage is not this run's
+        if net.x8:
+            net.ensure_x8()  # calibration (an evaluation of its own; a no-op after a model's load) before the first round
+            ops.split_overflow(reset=True)
+    n_class = net.P[f'{net.name}.heads'].shape[1]
+    trunc = ops.truncation_settings(top_k, top_p, n_class)
+    tex_flat, tex_host = _texture_ids(tex_tok, n_books)
+    n = tex_flat.numel()
+    if init is not None and (tuple(init[0].shape) != (n_books, n) or tuple(init[1].shape) != (n, )):
+        raise ValueError(f'init: source lists [{n_books}, {n}] and keep [{n}] expected, got '
+                         f'{tuple(init[0].shape)} / {tuple(init[1].shape)}')
+    return noise or TorchDeviceNoise(tex_tok.device), n_class, trunc, tex_flat, tex_host
+
+
+def _initial_state(init, tex_tok, n_books, mask_id, n_class, x_t=None, out=None):
+    """(x_t int64 [B, T], out int64 [n_books, B*T], err) before the first round, written into x_t / out if given: all masked
+    / all -1, or with init = (src_lists, keep) in tex_tok's sample order t2h_edit_prefill's state and error word."""
+    if x_t is None:
+        x_t = torch.empty(tuple(tex_tok.shape), dtype=torch.int64, device=tex_tok.device)
+        out = torch.empty((n_books, tex_tok.numel()), dtype=torch.int64, device=tex_tok.device)
+    if init is not None:
+        return x_t, out, ops.edit_prefill(init[0], tex_tok.view(-1), init[1], mask_id, n_class, x_t=x_t, out=out)
+    return x_t.fill_(mask_id), out.fill_(-1), None
+
+
+def _round(net, x_t, out, segm_tok, tex_tok, rows, n_rows, noise, temp, logits_ws, trunc_kw, defer=True, active=None):
+    """One round of the reference's loop: the transformer on x_t (defer: the last layer's tail on the listed rows only,
+    and only the first `active` samples), then the tokens of the first n_rows of `rows` drawn into x_t / out."""
+    compact = False
+    if defer:
+        net.hidden(x_t, segm_tok, tex_tok, defer_tail=True, active=active)
+        hidden, compact = net.finish_tail(rows, n_rows)
+    else:
+        hidden = net.hidden(x_t, segm_tok, tex_tok)
+    ops.sample_heads(hidden, *net.final_norm_and_heads(), {}, rows, n_rows, tex_tok.view(-1), temp, x_t, out,
+                     row_noise=noise, hidden_compact=compact, logits_ws=logits_ws, **trunc_kw)
 
 
 class RoundGraph:
@@ -727,8 +765,7 @@ class RoundGraph:
         in the middle of a later run would be an eager round + a device-wide synchronisation inside the sampling
         loop.  One eager round on a valid dummy state first (it
         sizes every lazily allocated workspace); a capture itself executes nothing.  Call on self.stream."""
-        self.x_t.fill_(self.mask_id)
-        self.out.fill_(-1)
+        _initial_state(None, self.tex, self.out.shape[0], self.mask_id, self.n_class, self.x_t, self.out)
         for t in (self.segm, self.tex, self.rows_tbl, self.offs_tbl, self.rng_tbl, self.round_ctr, self.seed):
             t.zero_()
         self.body(self.B)
@@ -739,16 +776,10 @@ class RoundGraph:
 
     def body(self, k):
         """One round on the first k samples of the batch (the others have no step left)."""
-        net = self._net()
-        P, nm = net.P, net.name
         ops.schedule_advance(self.rows_tbl, self.offs_tbl, self.rng_tbl, self.round_ctr, self.cur_rows, self.cur_offs,
                              self.cur_rng, self.maxr)
-        net.hidden(self.x_t, self.segm, self.tex, defer_tail=True, active=k)
-        hidden, compact = net.finish_tail(self.cur_rows, self.maxr)
-        ops.sample_heads(hidden, P[f'{nm}.ln_f.g'], P[f'{nm}.ln_f.b'], P[f'{nm}.heads'], {}, self.cur_rows, self.maxr,
-                         self.tex.view(-1), self.temp, self.x_t, self.out,
-                         row_noise=('philox', self.seed, self.cur_offs, self.cur_rng), hidden_compact=compact,
-                         logits_ws=self.logits_ws, **self.trunc)
+        _round(self._net(), self.x_t, self.out, self.segm, self.tex, self.cur_rows, self.maxr,
+               ('philox', self.seed, self.cur_offs, self.cur_rng), self.temp, self.logits_ws, self.trunc, active=k)
 
     def capture(self, k):
         g = torch.cuda.CUDAGraph()
@@ -786,12 +817,7 @@ class RoundGraph:
             self.rng_tbl[:R].copy_(torch.from_numpy(tables.aux32_tbl), non_blocking=False)
             self.segm.copy_(segm_tok)
             self.tex.copy_(tex_tok)
-            if init is not None:
-                ops.edit_prefill(init[0], self.tex.view(-1), init[1], self.mask_id, self.n_class, x_t=self.x_t,
-                                 out=self.out)
-            else:
-                self.x_t.fill_(self.mask_id)
-                self.out.fill_(-1)
+            _initial_state(init, self.tex, self.out.shape[0], self.mask_id, self.n_class, self.x_t, self.out)
             self.round_ctr.zero_()
             self.seed.fill_(schedule.as_int64(sched.seed))  # (a uint64 seed >= 2^63 in its two's-complement form)
             for r in range(R):
@@ -840,49 +866,29 @@ def sample_tokens(net, segm_tok, tex_tok, sample_steps, mask_id, temp=1.0, noise
     Test hooks, called after each round and allowed to overwrite x_t in place (teacher forcing):
     round_hook(r, steps, x_t, out) with steps[b] = the step sample b just took (0 = idle);
     step_hook(t, x_t, out) (compact=False only; steps that change no token are skipped)."""
-    P, nm = net.P, net.name
     B, T = segm_tok.shape
-    dev = segm_tok.device
-    split = bool(getattr(net, 'split', False))
-    if split:
-        ops.split_overflow(reset=True)  # a flag left by an earlier stage is not this run's
+    dev, n = segm_tok.device, B * T
     if compact is None:
         compact = step_hook is None and os.environ.get('T2H_COMPACT_ROUNDS', '1') != '0'
     if compact and step_hook is not None:
         raise ValueError('step_hook needs compact=False (samples are at different steps in a compact round)')
-    noise = noise or TorchDeviceNoise(dev)
-    n = B * T
-    n_class = P[f'{nm}.heads'].shape[1]
-    trunc = ops.truncation_settings(top_k, top_p, n_class)  # (raises before the generator has moved)
-    tex_flat = tex_tok.reshape(-1).contiguous()
+    noise, n_class, trunc, tex_flat, tex_host = _begin_run(net, tex_tok, n_books, noise, init, top_k, top_p)
     # finished samples leave the batch (T2H_SHRINK_BATCH=0 opts out; hooks see the batch in its own order)
     shrink = (compact and step_hook is None and round_hook is None and os.environ.get('T2H_SHRINK_BATCH', '1') != '0')
-    if split and getattr(net, 'x8', False):
-        net.ensure_x8()  # (a no-op after the model's load-time calibration; bare SamplerNets of tests / tools)
-        ops.split_overflow(reset=True)
-    if init is not None:
-        src_lists, keep = init
-        if tuple(src_lists.shape) != (n_books, n) or tuple(keep.shape) != (n, ):
-            raise ValueError(f'init: source lists [{n_books}, {n}] and keep [{n}] expected, got '
-                             f'{tuple(src_lists.shape)} / {tuple(keep.shape)}')
-    sched = build_schedule(tex_tok, sample_steps, n_books, n_class, noise, compact, shrink, init=init)
-    defer = bool(split and getattr(net, 'split_mha', False) and os.environ.get('T2H_TRIM_LAST_LAYER', '1') != '0')
+    sched = _schedule(tex_flat, tex_host, B, sample_steps, n_books, n_class, noise, compact, shrink, init)
+    defer = bool(net.split and net.split_mha and os.environ.get('T2H_TRIM_LAST_LAYER', '1') != '0')
     # (only the deferred-tail form of hidden() runs on the prefix of running samples; every other form evaluates the
     # whole batch each round, and the counts say so)
     net.last_stats = schedule.stats(sched.round_steps, sample_steps, sched.active if defer else None, kept=sched.kept)
+    tex_tok = tex_flat.view(B, T)
+    in_batch_order = lambda out: out  # [n_books, n] in the schedule's sample order -> the caller's
     if sched.perm is not None:
         perm_t = torch.from_numpy(sched.perm).to(dev)
         segm_tok, tex_tok = segm_tok[perm_t].contiguous(), tex_tok[perm_t].contiguous()
-        tex_flat = tex_tok.reshape(-1)
         if init is not None:  # the initial state in the schedule's sample order, like segm_tok / tex_tok
-            init = (src_lists.view(n_books, B, T)[:, perm_t].reshape(n_books, n).contiguous(),
-                    keep.view(B, T)[perm_t].reshape(n).contiguous())
-
-    def in_batch_order(out):  # [n_books, n] in the schedule's sample order -> the caller's
-        if sched.perm is None:
-            return out
-        inv = torch.from_numpy(np.argsort(sched.perm)).to(dev)
-        return out.view(out.shape[0], B, T)[:, inv].reshape(out.shape[0], n).contiguous()
+            init = (init[0].view(-1, B, T)[:, perm_t].reshape(-1, n).contiguous(), init[1].view(B, T)[perm_t].reshape(n))
+        caller_rows = torch.from_numpy(schedule.in_caller_order(sched.perm, B, T)).to(dev)
+        in_batch_order = lambda out: out[:, caller_rows]
 
     # Default (T2H_GRAPH=0 opts out): every round is ONE replay of a captured launch sequence (RoundGraph)
     # instead of ~180 launches from this thread.  The GPU work is the same; what changes is the host side --
@@ -896,36 +902,22 @@ def sample_tokens(net, segm_tok, tex_tok, sample_steps, mask_id, temp=1.0, noise
         # padded rows per round: a power of two >= 16 (at most five graph sets per batch size, whatever the seeds)
         maxr = min(net.TRIM_MAX_ROWS, max(16, 1 << (int(sched.max_rows) - 1).bit_length()))
         net._buffers(n, net.desc['C'], dev)  # (a change of batch size drops the graphs of the old buffers)
-        key = round_graph_key(B, T, sample_steps, maxr, temp, mask_id, n_books, getattr(net, 'x8', False), trunc)
+        key = round_graph_key(B, T, sample_steps, maxr, temp, mask_id, n_books, net.x8, trunc)
         if key not in net._graphs:
-            net._graphs[key] = RoundGraph(net, B, T, sample_steps, maxr, n_books, n_class, temp, mask_id, dev,
-                                          trunc=trunc)
+            net._graphs[key] = RoundGraph(net, B, T, sample_steps, maxr, n_books, n_class, temp, mask_id, dev, trunc=trunc)
         return in_batch_order(net._graphs[key].run(sched, segm_tok, tex_tok, init=init).clone())
-    if init is not None:
-        x_t = torch.empty((B, T), dtype=torch.int64, device=dev)
-        out = torch.empty((n_books, n), dtype=torch.int64, device=dev)
-        ops.edit_prefill(init[0], tex_flat, init[1], mask_id, n_class, x_t=x_t, out=out)
-    else:
-        x_t = torch.full((B, T), mask_id, dtype=torch.int64, device=dev)
-        out = torch.full((n_books, n), -1, dtype=torch.int64, device=dev)
+    x_t, out, _ = _initial_state(init, tex_tok, n_books, mask_id, n_class)
     logits_ws = torch.empty((max(sched.max_rows, 1), n_class), dtype=torch.float32, device=dev)
     for r in range(sched.n_rounds):
         lo, hi = int(sched.start[r]), int(sched.start[r + 1])
         k = int(sched.active[r]) if sched.active is not None else None
-        hidden = (net.hidden(x_t, segm_tok, tex_tok, defer_tail=True, active=k) if defer
-                  else net.hidden(x_t, segm_tok, tex_tok))
-        rows_r = sched.rows[lo:hi]
-        hidden_compact = False
-        if defer:
-            hidden, hidden_compact = net.finish_tail(rows_r, hi - lo)
-        ops.sample_heads(hidden, P[f'{nm}.ln_f.g'], P[f'{nm}.ln_f.b'], P[f'{nm}.heads'], {}, rows_r, hi - lo, tex_flat,
-                         temp, x_t, out, row_noise=sched.row_noise(lo, hi), hidden_compact=hidden_compact,
-                         logits_ws=logits_ws, **_trunc_kw(trunc))
+        _round(net, x_t, out, segm_tok, tex_tok, sched.rows[lo:hi], hi - lo, sched.row_noise(lo, hi), temp, logits_ws,
+               _trunc_kw(trunc), defer, k)
         if round_hook is not None:
             round_hook(r, sched.round_steps[r], x_t, out)
         if step_hook is not None:
             step_hook(int(sched.round_steps[r].max()), x_t, out)
-    if split:
+    if net.split:
         check_split_overflow('index sampler')
     return in_batch_order(out)
 
@@ -945,42 +937,20 @@ def sample_tokens_confidence(net, segm_tok, tex_tok, mask_id, rounds=16, temp=1.
     the token a row draws, never its confidence (the log-probability under the full softmax).  round_hook(r, x_t, out, tokens, conf, scores) is called after round
     r = 1 .. R and may overwrite x_t / out in place (teacher forcing); rounds after the last masked row of the whole
     batch are not evaluated (their draws are still counted).  Returns int64 [n_books, B*T] (-1 off-texture)."""
-    P, nm = net.P, net.name
     B, T = segm_tok.shape
-    dev = segm_tok.device
+    dev, n = segm_tok.device, B * T
     R = int(rounds)
     if R < 1:
         raise ValueError(f'rounds must be >= 1, got {rounds}')
     if not float(choice_temp) >= 0.0:
         raise ValueError(f'choice_temp must be >= 0, got {choice_temp}')
-    split = bool(getattr(net, 'split', False))
-    if split:
-        ops.split_overflow(reset=True)  # a flag left by an earlier stage is not this run's
-        if getattr(net, 'x8', False):
-            net.ensure_x8()  # calibration (an evaluation of its own) before the first round, never inside one
-            ops.split_overflow(reset=True)
-    noise = noise or TorchDeviceNoise(dev)
-    n = B * T
-    n_class = P[f'{nm}.heads'].shape[1]
-    trunc_kw = _trunc_kw(ops.truncation_settings(top_k, top_p, n_class))  # (raises before the generator has moved)
-    tex_flat = tex_tok.reshape(-1).contiguous()
-    tex_host = tex_flat.cpu().numpy()
-    if tex_host.size and (int(tex_host.min()) < 0 or int(tex_host.max()) >= n_books):
-        raise _lib.T2HError(f'texture ids must lie in [0, {n_books}), got [{int(tex_host.min())}, {int(tex_host.max())}]')
+    noise, n_class, trunc, tex_flat, _ = _begin_run(net, tex_tok, n_books, noise, init, top_k, top_p)
+    trunc_kw = _trunc_kw(trunc)
+    x_t, out, err = _initial_state(init, tex_flat.view(B, T), n_books, mask_id, n_class)
     m0 = np.full(B, T, dtype=np.int64)
     if init is not None:
-        src_lists, keep = init
-        if tuple(src_lists.shape) != (n_books, n) or tuple(keep.shape) != (n, ):
-            raise ValueError(f'init: source lists [{n_books}, {n}] and keep [{n}] expected, got '
-                             f'{tuple(src_lists.shape)} / {tuple(keep.shape)}')
-        x_t = torch.empty((B, T), dtype=torch.int64, device=dev)
-        out = torch.empty((n_books, n), dtype=torch.int64, device=dev)
-        err = ops.edit_prefill(src_lists, tex_flat, keep, mask_id, n_class, x_t=x_t, out=out)
-        kept = _init_check(err, keep, T)  # (raises before the generator has moved)
+        kept = _init_check(err, init[1], T)  # (raises before the generator has moved)
         m0 = T - kept.reshape(B, T).sum(1).astype(np.int64)
-    else:
-        x_t = torch.full((B, T), mask_id, dtype=torch.int64, device=dev)
-        out = torch.full((n_books, n), -1, dtype=torch.int64, device=dev)
     # the run's tables [R][w]: rows channel = k_r of every sample, 64-bit channel = generator offsets of the round's
     # exponential_ / rand draws, 32-bit channel = the bits of tau_r
     w = max(B, 2)
@@ -1016,7 +986,7 @@ def sample_tokens_confidence(net, segm_tok, tex_tok, mask_id, rounds=16, temp=1.
     scores = torch.empty(n, dtype=torch.float32, device=dev)
     group_ws = ops.confidence_group_ws(n, n_books, dev)
     logits_ws = torch.empty((n, n_class), dtype=torch.float32, device=dev)
-    lnf_g, lnf_b, heads = P[f'{nm}.ln_f.g'], P[f'{nm}.ln_f.b'], P[f'{nm}.heads']
+    lnf_g, lnf_b, heads = net.final_norm_and_heads()
     for r in range(1, n_eval + 1):
         ops.schedule_advance(k_dev, off_dev, tau_dev, ctr, cur_k, cur_off, cur_tau, w)
         if philox:
@@ -1035,7 +1005,7 @@ def sample_tokens_confidence(net, segm_tok, tex_tok, mask_id, rounds=16, temp=1.
         for r in range(n_eval + 1, R + 1):
             noise.exponential(r, None, (n, n_class))
             noise.uniform(r, (n, ))
-    if split:
+    if net.split:
         check_split_overflow('index sampler')
     return out
 

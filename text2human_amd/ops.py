@@ -886,6 +886,17 @@ def truncation_threshold(logits, top_k=None, top_p=None, scope=0):
     return theta, kept
 
 
+def _philox_fields(a, numel, device, **fields):
+    """philox_seed (philox_offset: of a whole-tensor draw of `numel` floats): ints, or int64 device tensors a replay reads"""
+    for name, v in fields.items():
+        if torch.is_tensor(v):
+            assert v.dtype == torch.int64 and v.is_cuda and (v.numel() == 1 if name == 'philox_seed' else v.numel() >= 1)
+            setattr(a, name + '_dev', v.data_ptr())
+        else:
+            setattr(a, name, int(v) & 0xFFFFFFFFFFFFFFFF)
+    a.philox_grid_threads = torch_draw_geometry(numel, device)[0]
+
+
 def sample_heads(hidden, lnf_g, lnf_b, w_heads, expo_by_head, rows, n_rows, tex, temp, x_t, out_idx, split=True,
                  philox=None, hidden_compact=False, row_noise=None, logits_ws=None, top_k=0, top_p=1.0):
     """All heads in one launch: `rows` (int32, first n_rows valid) are the changed token
@@ -931,12 +942,7 @@ def sample_heads(hidden, lnf_g, lnf_b, w_heads, expo_by_head, rows, n_rows, tex,
                 rr = row_noise[3]
                 assert rr.dtype == torch.int32 and rr.is_cuda and rr.numel() >= int(n_rows)
                 a.rng_rows = rr.data_ptr()
-            if torch.is_tensor(seed):  # the seed lives in device memory (graph replay)
-                assert seed.dtype == torch.int64 and seed.is_cuda and seed.numel() == 1
-                a.philox_seed_dev = seed.data_ptr()
-            else:
-                a.philox_seed = int(seed)
-            a.philox_grid_threads = torch_draw_geometry(n * n_class, hidden.device)[0]
+            _philox_fields(a, n * n_class, hidden.device, philox_seed=seed)  # (a tensor: the seed of a replayed round)
         else:
             _, erows, slots = row_noise
             _chk_f32(erows)
@@ -944,11 +950,9 @@ def sample_heads(hidden, lnf_g, lnf_b, w_heads, expo_by_head, rows, n_rows, tex,
             assert slots.dtype == torch.int32 and slots.is_cuda and slots.numel() >= int(n_rows)
             a.expo_rows, a.expo_slot = erows.data_ptr(), slots.data_ptr()
     elif philox is not None:
-        seed, offsets = philox
-        a.philox_seed = int(seed)
-        for h, off in offsets.items():
+        _philox_fields(a, n * n_class, hidden.device, philox_seed=philox[0])
+        for h, off in philox[1].items():
             a.philox_offset[h] = int(off)
-        a.philox_grid_threads = torch_draw_geometry(n * n_class, hidden.device)[0]
     check(_lib.load().t2h_sample_heads(ctypes.byref(a), _stream()), 't2h_sample_heads')
 
 
@@ -956,18 +960,6 @@ def confidence_group_ws(n, n_heads, device):
     """Workspace of confidence_tail's grouping launch (int32)."""
     return torch.empty(int(_lib.load().t2h_confidence_group_ws_ints(int(n), int(n_heads))), dtype=torch.int32,
                        device=device)
-
-
-def _philox_fields(a, noise, numel, device):
-    """noise = ('philox', seed, offset): ints, or int64 device tensors (values a replayed round reads from memory)."""
-    _, seed, off = noise
-    for name, v in (('philox_seed', seed), ('philox_offset', off)):
-        if torch.is_tensor(v):
-            assert v.dtype == torch.int64 and v.is_cuda and v.numel() >= 1
-            setattr(a, name + '_dev', v.data_ptr())
-        else:
-            setattr(a, name, int(v) & 0xFFFFFFFFFFFFFFFF)
-    a.philox_grid_threads = torch_draw_geometry(numel, device)[0]
 
 
 def confidence_tail(hidden, lnf_g, lnf_b, w_heads, tex, x_t, mask_id, temp, noise, tok, conf, group_ws=None,
@@ -999,7 +991,7 @@ def confidence_tail(hidden, lnf_g, lnf_b, w_heads, tex, x_t, mask_id, temp, nois
         assert e.is_contiguous() and e.numel() == n * n_class
         a.expo = e.data_ptr()
     else:
-        _philox_fields(a, noise, n * n_class, dev)
+        _philox_fields(a, n * n_class, dev, philox_seed=noise[1], philox_offset=noise[2])
     a.group_ws, a.logits_ws, a.tok, a.conf = group_ws.data_ptr(), logits_ws.data_ptr(), tok.data_ptr(), conf.data_ptr()
     check(_lib.load().t2h_confidence_tail(ctypes.byref(a), _stream()), 't2h_confidence_tail')
     return tok, conf
@@ -1024,7 +1016,7 @@ def confidence_commit(conf, tok, tex, noise, k, tau, mask_id, x_t, out, n_class,
         assert u.is_contiguous() and u.numel() == n
         a.u = u.data_ptr()
     else:
-        _philox_fields(a, noise, n, x_t.device)
+        _philox_fields(a, n, x_t.device, philox_seed=noise[1], philox_offset=noise[2])
     a.k, a.tau, a.mask_id, a.x_t, a.out = k.data_ptr(), tau.data_ptr(), int(mask_id), x_t.data_ptr(), out.data_ptr()
     if scores is not None:
         _chk_f32(scores)

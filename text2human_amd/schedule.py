@@ -19,6 +19,8 @@ consequences, both used by engine.sample_tokens:
 This module is host-side integer bookkeeping (numpy); the draws themselves are reproduced on the
 device (t2h_unmask_schedule / t2h_sample_heads) or taken from an explicit noise source.
 """
+from collections import namedtuple
+
 import numpy as np
 
 
@@ -117,6 +119,42 @@ def leave_order(step_of_row, B, T, kept=None):
     n_act = np.array([len(np.unique(steps[b][live[b]])) for b in range(B)], dtype=np.int64)
     perm = np.argsort(-n_act, kind='stable').astype(np.int64)
     return perm, n_act[perm]
+
+
+# plan_rounds' result, in the SCHEDULE's sample order.  perm int64 [B]: new position -> original sample (None: the caller's
+# order); order / start / round_steps: group_rounds; active int64 [R]: samples still running in round r, a prefix of the
+# batch; rng_rows int32 / offs int64: of every listed row, its row in the caller's batch / its draw's generator offset.
+RoundPlan = namedtuple('RoundPlan', 'perm order start round_steps kept active rng_rows offs')
+
+
+def plan_rounds(step_of_row, tex_host, B, T, compact, shrink, kept=None, expo_off=None):
+    """What engine.build_schedule decides on the host from what the device hands back (step_of_row, tex_host, kept:
+    [B*T], the caller's order) and draw_offsets' expo_off.  shrink (compact only): finished samples leave the batch."""
+    perm = rng_rows = active = offs = None
+    if shrink and compact and B > 1:
+        perm, _ = leave_order(step_of_row, B, T, kept)
+        if (perm == np.arange(B)).all():
+            perm = None
+    if perm is not None:
+        orig_row = (perm[:, None] * T + np.arange(T)[None, :]).reshape(-1)  # original row of every reordered row
+        step_of_row, tex_host = step_of_row[orig_row], tex_host[orig_row]
+        kept = kept[orig_row] if kept is not None else None
+    order, start, round_steps = group_rounds(step_of_row, B, T, compact, kept)
+    if expo_off is not None:
+        offs = expo_off[step_of_row[order], tex_host[order]]
+        assert (offs >= 0).all()
+    if shrink and compact:
+        active = (round_steps > 0).sum(1).astype(np.int64)
+        assert all((round_steps[r, :active[r]] > 0).all() for r in range(len(active)))  # a prefix of the batch
+    if perm is not None:
+        rng_rows = orig_row[order].astype(np.int32)
+    return RoundPlan(perm, order, start, round_steps, kept, active, rng_rows, offs)
+
+
+def in_caller_order(perm, B, T):
+    """int64 [B*T]: x[..., in_caller_order(perm, B, T)] = the token rows x of a batch reordered by `perm`, as the caller had them"""
+    inv = np.arange(B) if perm is None else np.argsort(perm)
+    return (inv[:, None] * T + np.arange(T)[None, :]).reshape(-1)
 
 
 def padded_tables(order, per_row, start, maxr):
