@@ -498,6 +498,32 @@ int t2h_confidence_commit(const t2h_confidence_commit_args* args, void* stream);
 int t2h_truncation_threshold(const float* logits, int32_t n_rows, int32_t n_class, int32_t top_k, uint32_t top_p_q,
                              int32_t scope, float* theta, int32_t* kept, void* stream);
 
+/* Per-image sampling controls ("Per-image sampling controls"): the same tails with temp / top_k / top_p_q
+ * taken PER SAMPLE from a table in device memory instead of from the argument struct (whose temp / top_k / top_p_q are
+ * then not read).  Token row r belongs to sample r / rows_per_sample -- the batch as the kernels see it; a host that
+ * reorders the samples reorders the table with them -- and is computed exactly as the scalar entry point called with
+ * params[r / rows_per_sample] computes it: the same logits (divided by that temp), the same threshold, the same race on
+ * the same noise.  rows_per_sample must divide n; n_class <= 2048 (any sample may use top-p).  The table's values are
+ * the CALLER's to validate (temp > 0, top_k >= 0, top_p_q <= 2^20); a sample whose rules cut nothing (top_k 0 or >=
+ * n_class, top_p_q 0 or 2^20) keeps every class and draws the token of the launch without truncation.
+ * t2h_confidence_commit_per_sample: args->tau is float [B], sample b's own tau (t2h_confidence_commit reads tau[0]);
+ *   k [B] is per sample already.
+ * t2h_truncation_threshold_per_row: t2h_truncation_threshold with row r's rules = params[r / rows_per_sample]
+ *   (rows_per_sample divides n_rows). */
+typedef struct t2h_sample_params {
+  float temp;
+  int32_t top_k;
+  uint32_t top_p_q;
+} t2h_sample_params;
+int t2h_sample_heads_per_sample(const t2h_sample_heads_args* args, const t2h_sample_params* params,
+                                int32_t rows_per_sample, void* stream);
+int t2h_confidence_tail_per_sample(const t2h_confidence_tail_args* args, const t2h_sample_params* params,
+                                   int32_t rows_per_sample, void* stream);
+int t2h_confidence_commit_per_sample(const t2h_confidence_commit_args* args, void* stream);
+int t2h_truncation_threshold_per_row(const float* logits, int32_t n_rows, int32_t n_class,
+                                     const t2h_sample_params* params, int32_t rows_per_sample, int32_t scope,
+                                     float* theta, int32_t* kept, void* stream);
+
 /* Sampler training-time forward (models/transformer_model.py:212-274, forward only).
  * q_sample: mask[b,i] = u[b,i] < t[b] / num_timesteps; x_t = mask ? mask_id : x0.
  * masked_ce_heads: sum over the 18 heads of F.cross_entropy(logits_h, gt_h, ignore_index=-1,

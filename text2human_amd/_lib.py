@@ -88,6 +88,11 @@ class ConfidenceCommitArgs(ctypes.Structure):
     ]
 
 
+class SampleParams(ctypes.Structure):
+    """struct t2h_sample_params (include/t2h_hip.h): one entry per sample of a per-image table."""
+    _fields_ = [('temp', c_f32), ('top_k', c_i32), ('top_p_q', ctypes.c_uint32)]
+
+
 # name -> (restype, argtypes); must list EVERY symbol declared in include/t2h_hip.h
 SIGNATURES = {
     't2h_gemm_split_f32': (ctypes.c_int, [ctypes.POINTER(GemmSplitArgs), c_vp]),
@@ -132,6 +137,10 @@ SIGNATURES = {
     't2h_confidence_tail': (ctypes.c_int, [ctypes.POINTER(ConfidenceTailArgs), c_vp]),
     't2h_confidence_commit': (ctypes.c_int, [ctypes.POINTER(ConfidenceCommitArgs), c_vp]),
     't2h_truncation_threshold': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, ctypes.c_uint32, c_i32, c_vp, c_vp, c_vp]),
+    't2h_sample_heads_per_sample': (ctypes.c_int, [ctypes.POINTER(SampleHeadsArgs), c_vp, c_i32, c_vp]),
+    't2h_confidence_tail_per_sample': (ctypes.c_int, [ctypes.POINTER(ConfidenceTailArgs), c_vp, c_i32, c_vp]),
+    't2h_confidence_commit_per_sample': (ctypes.c_int, [ctypes.POINTER(ConfidenceCommitArgs), c_vp]),
+    't2h_truncation_threshold_per_row': (ctypes.c_int, [c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
     't2h_absmax_f32': (ctypes.c_int, [c_vp, c_i32, c_i64, c_i32, c_vp, c_vp]),
     't2h_split_rows_absmax': (ctypes.c_int, [c_vp, c_i64, c_i32, c_vp, c_vp]),
     't2h_gather_rows': (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]),

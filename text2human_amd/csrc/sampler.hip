@@ -180,12 +180,32 @@ __device__ __forceinline__ uint32_t trunc_select(const float* lg, int n_class, f
   return floor_key;
 }
 
+// ---- per-image sampling controls ("Per-image sampling controls").  The PER_SAMPLE instances of the tail
+// kernels take temp / top_k / top_p_q of row `row` from params[row / T] (T = rows per sample, the batch in its device
+// order) instead of the launch's scalars; everything else is the scalar instance's code.  The table lives in device
+// memory, so the values are normalised here the way trunc_settings normalises the scalars on the host: an image whose
+// rules cut nothing has (0, 0) and skips the selection (theta = -inf: every class enters the race).
+struct sample_settings {
+  float temp;
+  int top_k;
+  uint32_t top_p_q;
+};
+__device__ __forceinline__ sample_settings sample_settings_of(const t2h_sample_params* __restrict__ params, int row, int T,
+                                                             int n_class) {
+  const t2h_sample_params p = params[row / T];  // (row is uniform over the wave: one scalar load)
+  sample_settings s;
+  s.temp = p.temp;
+  s.top_k = (p.top_k <= 0 || p.top_k >= n_class) ? 0 : p.top_k;
+  s.top_p_q = p.top_p_q >= (1u << 20) ? 0u : p.top_p_q;
+  return s;
+}
+
 // One workgroup per token row; rows that are not (changed && of this head's
 // texture) exit at once.  LN_f -> 512->n_class head (wave-cooperative dot
 // products, coalesced weight rows) -> exponential-race argmax.
 constexpr int SH_THREADS = 1024;
 
-template <int C, bool TRUNC = false>
+template <int C, bool TRUNC = false, bool PER_SAMPLE = false>
 __device__ __forceinline__ void sample_row(float* lds, int row, const float* __restrict__ hidden,
                                            const float* __restrict__ g, const float* __restrict__ bta,
                                            const float* __restrict__ w, const float* __restrict__ expo, int head,
@@ -257,7 +277,8 @@ __device__ __forceinline__ void sample_row(float* lds, int row, const float* __r
   if constexpr (TRUNC) {
     __shared__ trunc_lds tr;
     int kept;
-    theta = trunc_unkey(trunc_select<SH_THREADS>(lds, n_class, mx, top_k, top_p_q, &tr, tid, &kept));
+    if (!PER_SAMPLE || top_k != 0 || top_p_q != 0)  // (uniform over the workgroup)
+      theta = trunc_unkey(trunc_select<SH_THREADS>(lds, n_class, mx, top_k, top_p_q, &tr, tid, &kept));
   }
   // argmax_j exp(l_j - max) / q_j  (first index wins ties)
   const float* er = expo + (int64_t)row * n_class;
@@ -633,8 +654,9 @@ __global__ void schedule_advance_kernel(const int32_t* __restrict__ rows_tbl, co
 // bit-identical to the one-launch form.
 constexpr int SL_SPLIT = 8, SL_THREADS = 256;
 
-template <int C>
-__global__ __launch_bounds__(SL_THREADS) void sample_logits_kernel(const t2h_sample_heads_args a, float* __restrict__ ws) {
+template <int C, bool PER_SAMPLE>
+__global__ __launch_bounds__(SL_THREADS) void sample_logits_kernel(const t2h_sample_heads_args a, float* __restrict__ ws,
+                                                                   const t2h_sample_params* __restrict__ params, int T) {
   constexpr int VPL = C / 256;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int slot = blockIdx.x / SL_SPLIT, part = blockIdx.x - slot * SL_SPLIT;
@@ -665,7 +687,7 @@ __global__ __launch_bounds__(SL_THREADS) void sample_logits_kernel(const t2h_sam
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[i][e] = (v[i][e] - mean) * rstd * gg[e] + bb[e];
   }
-  const float temp = a.temp;
+  const float temp = PER_SAMPLE ? params[row / T].temp : a.temp;
   const float* w = a.w_heads + (int64_t)head * a.n_class * C;
   const int per = (a.n_class + SL_SPLIT - 1) / SL_SPLIT;
   const int j_end = min(a.n_class, (part + 1) * per);
@@ -693,8 +715,9 @@ __global__ __launch_bounds__(SL_THREADS) void sample_logits_kernel(const t2h_sam
   }
 }
 
-template <bool TRUNC>
-__global__ __launch_bounds__(SH_THREADS) void sample_pick_kernel(const t2h_sample_heads_args a, const float* __restrict__ ws) {
+template <bool TRUNC, bool PER_SAMPLE>
+__global__ __launch_bounds__(SH_THREADS) void sample_pick_kernel(const t2h_sample_heads_args a, const float* __restrict__ ws,
+                                                                 const t2h_sample_params* __restrict__ params, int T) {
   __shared__ float red[2 * (SH_THREADS / 64)];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   constexpr int NW = SH_THREADS / 64;
@@ -713,7 +736,15 @@ __global__ __launch_bounds__(SH_THREADS) void sample_pick_kernel(const t2h_sampl
   if constexpr (TRUNC) {
     __shared__ trunc_lds tr;
     int kept;
-    theta = trunc_unkey(trunc_select<SH_THREADS>(lg, a.n_class, mx, a.top_k, a.top_p_q, &tr, tid, &kept));
+    int top_k = a.top_k;
+    uint32_t top_p_q = a.top_p_q;
+    if constexpr (PER_SAMPLE) {
+      const sample_settings st = sample_settings_of(params, row, T, a.n_class);
+      top_k = st.top_k;
+      top_p_q = st.top_p_q;
+    }
+    if (!PER_SAMPLE || top_k != 0 || top_p_q != 0)  // (uniform over the workgroup)
+      theta = trunc_unkey(trunc_select<SH_THREADS>(lg, a.n_class, mx, top_k, top_p_q, &tr, tid, &kept));
   }
   // noise of this row: explicit compact rows (expo_rows[expo_slot[slot]]), the head's explicit full
   // tensor, or computed -- at the row's own generator offset when the list mixes steps
@@ -768,16 +799,19 @@ __global__ __launch_bounds__(SH_THREADS) void sample_pick_kernel(const t2h_sampl
 
 // All heads in one launch: one workgroup per CHANGED token (compact list from
 // unmask_step), which picks the head / noise tensor of its own texture.
-template <int C, bool TRUNC>
-__global__ __launch_bounds__(SH_THREADS) void sample_heads_kernel(const t2h_sample_heads_args a) {
+template <int C, bool TRUNC, bool PER_SAMPLE>
+__global__ __launch_bounds__(SH_THREADS) void sample_heads_kernel(const t2h_sample_heads_args a,
+                                                                  const t2h_sample_params* __restrict__ params, int T) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int row = a.rows[blockIdx.x];
   const int head = (int)a.tex[row];
   const float* expo = a.expo[head];
   if (expo == nullptr) return;  // cannot happen: a head with changed tokens always drew its noise
-  sample_row<C, TRUNC>(lds, row, a.hidden, a.lnf_gamma, a.lnf_beta, a.w_heads + (int64_t)head * a.n_class * C, expo,
-                       head, a.temp, a.x_t, a.out_idx + (int64_t)head * a.n, a.n_class, a.top_k,
-                       a.top_p_q);  // (full hidden only)
+  sample_settings st = {a.temp, a.top_k, a.top_p_q};
+  if constexpr (PER_SAMPLE) st = sample_settings_of(params, row, T, a.n_class);
+  sample_row<C, TRUNC, PER_SAMPLE>(lds, row, a.hidden, a.lnf_gamma, a.lnf_beta, a.w_heads + (int64_t)head * a.n_class * C,
+                                   expo, head, st.temp, a.x_t, a.out_idx + (int64_t)head * a.n, a.n_class, st.top_k,
+                                   st.top_p_q);  // (full hidden only)
 }
 
 // ---- confidence-ordered parallel decoding ("Confidence-ordered decoding").  A round samples EVERY masked
@@ -828,8 +862,11 @@ __global__ __launch_bounds__(1024) void conf_group_kernel(const int64_t* __restr
 
 // One workgroup per (tile, class quarter): LN_f of the tile's rows into LDS (one wave per row, the arithmetic of
 // sample_row), then every wave streams 4 weight rows at a time and uses them for all rows of the tile.
-template <int C>
-__global__ __launch_bounds__(CT_THREADS) void conf_logits_kernel(const t2h_confidence_tail_args a) {
+// PER_SAMPLE: the rows of a tile share a head, not an image -- the temperature is per ROW of the tile (lane r of
+// every wave holds row r's, read back with v_readlane: no LDS beyond xs, whose 32 KiB fit five times into a CU's).
+template <int C, bool PER_SAMPLE>
+__global__ __launch_bounds__(CT_THREADS) void conf_logits_kernel(const t2h_confidence_tail_args a,
+                                                                 const t2h_sample_params* __restrict__ params, int T) {
   constexpr int VPL = C / 256, NW = CT_THREADS / 64;
   __shared__ __attribute__((aligned(16))) float xs[CT_ROWS * C];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -869,6 +906,10 @@ __global__ __launch_bounds__(CT_THREADS) void conf_logits_kernel(const t2h_confi
   }
   __syncthreads();
   const float temp = a.temp;
+  float row_temp = 1.f;
+  if constexpr (PER_SAMPLE) {
+    if (lane < cnt) row_temp = params[rows[lane] / T].temp;
+  }
   const float* w = a.w_heads + (int64_t)head * a.n_class * C;
   const int per = (a.n_class + CT_SPLIT - 1) / CT_SPLIT;
   const int j_end = min(a.n_class, (part + 1) * per);
@@ -895,10 +936,12 @@ __global__ __launch_bounds__(CT_THREADS) void conf_logits_kernel(const t2h_confi
         acc[u] = t;
       }
       float* lg = a.logits_ws + (int64_t)rows[r] * a.n_class;
+      const float tr = PER_SAMPLE ? __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, row_temp), r))
+                                  : temp;
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const float res = wave_sum(acc[u]);
-        if (lane == 0 && j0 + u < j_end) lg[j0 + u] = res / temp;
+        if (lane == 0 && j0 + u < j_end) lg[j0 + u] = res / tr;
       }
     }
   }
@@ -907,8 +950,9 @@ __global__ __launch_bounds__(CT_THREADS) void conf_logits_kernel(const t2h_confi
 // One wave per row: max, the exponential race of sample_pick_kernel (same scores, lowest index of the maximum), the
 // sum of the same exponentials, and the log-probability of the drawn class.
 constexpr int CP_ROWS = 4;
-template <bool TRUNC>
-__global__ __launch_bounds__(64 * CP_ROWS) void conf_pick_kernel(const t2h_confidence_tail_args a) {
+template <bool TRUNC, bool PER_SAMPLE>
+__global__ __launch_bounds__(64 * CP_ROWS) void conf_pick_kernel(const t2h_confidence_tail_args a,
+                                                                 const t2h_sample_params* __restrict__ params, int T) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * CP_ROWS + (threadIdx.x >> 6);
   if (row >= a.n) return;  // (uniform over the wave)
@@ -928,7 +972,15 @@ __global__ __launch_bounds__(64 * CP_ROWS) void conf_pick_kernel(const t2h_confi
   if constexpr (TRUNC) {  // only the token changes: se / conf below stay those of the full softmax
     __shared__ trunc_lds tr[CP_ROWS];
     int kept;
-    theta = trunc_unkey(trunc_select<64>(lg, a.n_class, mx, a.top_k, a.top_p_q, &tr[threadIdx.x >> 6], lane, &kept));
+    int top_k = a.top_k;
+    uint32_t top_p_q = a.top_p_q;
+    if constexpr (PER_SAMPLE) {
+      const sample_settings st = sample_settings_of(params, __builtin_amdgcn_readfirstlane(row), T, a.n_class);
+      top_k = st.top_k;
+      top_p_q = st.top_p_q;
+    }
+    if (!PER_SAMPLE || top_k != 0 || top_p_q != 0)  // (uniform over the wave)
+      theta = trunc_unkey(trunc_select<64>(lg, a.n_class, mx, top_k, top_p_q, &tr[threadIdx.x >> 6], lane, &kept));
   }
   const float* er = a.expo ? a.expo + (int64_t)row * a.n_class : nullptr;
   const uint64_t pseed = a.philox_seed_dev ? *a.philox_seed_dev : a.philox_seed;
@@ -970,12 +1022,13 @@ __device__ __forceinline__ bool conf_before(float sj, int j, float si, int i) { 
   if (nj || ni) return nj == ni ? j < i : ni;
   return sj > si || (sj == si && j < i);
 }
+template <bool PER_SAMPLE>  // PER_SAMPLE: a.tau is [B], the sample's own choice temperature
 __global__ __launch_bounds__(CC_THREADS) void conf_commit_kernel(const t2h_confidence_commit_args a) {
   __shared__ float s_s[CC_MAX_T];
   __shared__ int m_s[CC_MAX_T];
   const int b = blockIdx.x, tid = threadIdx.x, T = a.T;
   const int k = a.k[b];
-  const float tau = *a.tau;
+  const float tau = PER_SAMPLE ? a.tau[b] : *a.tau;
   const uint64_t pseed = a.philox_seed_dev ? *a.philox_seed_dev : a.philox_seed;
   const uint64_t poff = a.philox_offset_dev ? *a.philox_offset_dev : a.philox_offset;
   for (int i = tid; i < T; i += CC_THREADS) {
@@ -1010,10 +1063,10 @@ __global__ __launch_bounds__(CC_THREADS) void conf_commit_kernel(const t2h_confi
 
 // ---- t2h_truncation_threshold: the selection alone, at the scope of sample_pick_kernel (one workgroup per row) or of
 // conf_pick_kernel (one wave per row); the row maximum is formed as those kernels form it.
-template <int NT>
+template <int NT, bool PER_SAMPLE>
 __global__ __launch_bounds__(NT == 64 ? 64 * CP_ROWS : SH_THREADS) void trunc_threshold_kernel(
     const float* __restrict__ logits, int n_rows, int n_class, int top_k, uint32_t top_p_q, float* __restrict__ theta,
-    int* __restrict__ kept) {
+    int* __restrict__ kept, const t2h_sample_params* __restrict__ params, int T) {
   constexpr int ROWS = NT == 64 ? CP_ROWS : 1, NW = NT / 64;
   __shared__ trunc_lds tr[ROWS];
   __shared__ float red[SH_THREADS / 64];
@@ -1021,6 +1074,11 @@ __global__ __launch_bounds__(NT == 64 ? 64 * CP_ROWS : SH_THREADS) void trunc_th
   const int row = NT == 64 ? blockIdx.x * CP_ROWS + wave : blockIdx.x;
   if (row >= n_rows) return;  // (uniform over the wave; the workgroup form has one row per workgroup)
   const int t = NT == 64 ? lane : (int)threadIdx.x;
+  if constexpr (PER_SAMPLE) {
+    const sample_settings st = sample_settings_of(params, __builtin_amdgcn_readfirstlane(row), T, n_class);
+    top_k = st.top_k;
+    top_p_q = st.top_p_q;
+  }
   const float* lg = logits + (int64_t)row * n_class;
   float mx = -INFINITY;
   for (int j = t; j < n_class; j += NT) mx = fmaxf(mx, lg[j]);
@@ -1053,21 +1111,44 @@ static inline bool trunc_settings(int32_t n_class, int32_t* top_k, uint32_t* top
               name ": top_k=%d / top_p_q=%u out of range (top_k >= 0, top_p_q <= 2^20; top-p: n_class <= 2048)",     \
               (int)(a_top_k), (unsigned)(a_top_p_q))
 
+// A per-sample table sits in device memory: its VALUES are the caller's to validate (ops.sampling_params); the kernels
+// treat anything that cuts nothing as off.  Any image may use top-p, so its class limit holds for the whole launch.
+#define T2H_PER_SAMPLE_REQUIRE(name, params, T, n, a_n_class)                                                          \
+  T2H_REQUIRE((params) != nullptr && (T) > 0 && (n) % (T) == 0 && (a_n_class) <= 2048,                                 \
+              name ": params[n / rows_per_sample] expected, rows_per_sample=%d dividing n=%d; n_class <= 2048", (int)(T), \
+              (int)(n))
+
+template <bool PER_SAMPLE>
+static int trunc_threshold_launch(const float* logits, int32_t n_rows, int32_t n_class, int32_t top_k, uint32_t top_p_q,
+                                  const t2h_sample_params* params, int32_t T, int32_t scope, float* theta, int32_t* kept,
+                                  void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (scope == 0)
+    hipLaunchKernelGGL((trunc_threshold_kernel<SH_THREADS, PER_SAMPLE>), dim3(n_rows), dim3(SH_THREADS), 0, s, logits,
+                       n_rows, n_class, top_k, top_p_q, theta, kept, params, T);
+  else
+    hipLaunchKernelGGL((trunc_threshold_kernel<64, PER_SAMPLE>), dim3((n_rows + CP_ROWS - 1) / CP_ROWS), dim3(64 * CP_ROWS),
+                       0, s, logits, n_rows, n_class, top_k, top_p_q, theta, kept, params, T);
+  T2H_CHECK_LAUNCH("t2h_truncation_threshold");
+  return T2H_OK;
+}
+
 extern "C" int t2h_truncation_threshold(const float* logits, int32_t n_rows, int32_t n_class, int32_t top_k,
                                         uint32_t top_p_q, int32_t scope, float* theta, int32_t* kept, void* stream) {
   T2H_REQUIRE(logits && theta && kept, "t2h_truncation_threshold: NULL pointer");
   T2H_REQUIRE(n_rows > 0 && n_class > 0 && (scope == 0 || scope == 1), "t2h_truncation_threshold: bad arguments");
   T2H_TRUNC_REQUIRE("t2h_truncation_threshold", top_k, top_p_q, n_class);
   trunc_settings(n_class, &top_k, &top_p_q);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (scope == 0)
-    hipLaunchKernelGGL(trunc_threshold_kernel<SH_THREADS>, dim3(n_rows), dim3(SH_THREADS), 0, s, logits, n_rows, n_class,
-                       top_k, top_p_q, theta, kept);
-  else
-    hipLaunchKernelGGL(trunc_threshold_kernel<64>, dim3((n_rows + CP_ROWS - 1) / CP_ROWS), dim3(64 * CP_ROWS), 0, s,
-                       logits, n_rows, n_class, top_k, top_p_q, theta, kept);
-  T2H_CHECK_LAUNCH("t2h_truncation_threshold");
-  return T2H_OK;
+  return trunc_threshold_launch<false>(logits, n_rows, n_class, top_k, top_p_q, nullptr, 0, scope, theta, kept, stream);
+}
+
+extern "C" int t2h_truncation_threshold_per_row(const float* logits, int32_t n_rows, int32_t n_class,
+                                                const t2h_sample_params* params, int32_t rows_per_sample, int32_t scope,
+                                                float* theta, int32_t* kept, void* stream) {
+  T2H_REQUIRE(logits && theta && kept, "t2h_truncation_threshold_per_row: NULL pointer");
+  T2H_REQUIRE(n_rows > 0 && n_class > 0 && (scope == 0 || scope == 1), "t2h_truncation_threshold_per_row: bad arguments");
+  T2H_PER_SAMPLE_REQUIRE("t2h_truncation_threshold_per_row", params, rows_per_sample, n_rows, n_class);
+  return trunc_threshold_launch<true>(logits, n_rows, n_class, 0, 0, params, rows_per_sample, scope, theta, kept, stream);
 }
 
 extern "C" int64_t t2h_confidence_group_ws_ints(int32_t n, int32_t n_heads) {
@@ -1075,9 +1156,13 @@ extern "C" int64_t t2h_confidence_group_ws_ints(int32_t n, int32_t n_heads) {
   return (int64_t)CT_HDR + 3 * (int64_t)conf_max_tiles(n, n_heads) + n;
 }
 
-extern "C" int t2h_confidence_tail(const t2h_confidence_tail_args* args, void* stream) {
+// params == NULL: the launch's scalars (t2h_confidence_tail); else the PER_SAMPLE instances (a.temp / a.top_k /
+// a.top_p_q are not read)
+static int confidence_tail_launch(const t2h_confidence_tail_args* args, const t2h_sample_params* params, int32_t T,
+                                  void* stream) {
   T2H_REQUIRE(args != nullptr, "t2h_confidence_tail: args is NULL");
   t2h_confidence_tail_args a = *args;
+  if (params) a.temp = 1.f, a.top_k = 0, a.top_p_q = 0;
   T2H_REQUIRE(a.hidden && a.lnf_gamma && a.lnf_beta && a.w_heads && a.tex && a.x_t && a.group_ws && a.logits_ws &&
                   a.tok && a.conf,
               "t2h_confidence_tail: NULL pointer");
@@ -1091,16 +1176,34 @@ extern "C" int t2h_confidence_tail(const t2h_confidence_tail_args* args, void* s
   const bool trunc = trunc_settings(a.n_class, &a.top_k, &a.top_p_q);
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(conf_group_kernel, dim3(1), dim3(1024), 0, s, a.x_t, a.tex, a.mask_id, a.n, a.n_heads, a.group_ws);
-  hipLaunchKernelGGL(conf_logits_kernel<512>, dim3(conf_max_tiles(a.n, a.n_heads) * CT_SPLIT), dim3(CT_THREADS), 0, s, a);
-  if (trunc)
-    hipLaunchKernelGGL(conf_pick_kernel<true>, dim3((a.n + CP_ROWS - 1) / CP_ROWS), dim3(64 * CP_ROWS), 0, s, a);
-  else
-    hipLaunchKernelGGL(conf_pick_kernel<false>, dim3((a.n + CP_ROWS - 1) / CP_ROWS), dim3(64 * CP_ROWS), 0, s, a);
+  const dim3 lgrid(conf_max_tiles(a.n, a.n_heads) * CT_SPLIT), pgrid((a.n + CP_ROWS - 1) / CP_ROWS);
+  if (params) {
+    T2H_PER_SAMPLE_REQUIRE("t2h_confidence_tail_per_sample", params, T, a.n, a.n_class);
+    hipLaunchKernelGGL((conf_logits_kernel<512, true>), lgrid, dim3(CT_THREADS), 0, s, a, params, T);
+    hipLaunchKernelGGL((conf_pick_kernel<true, true>), pgrid, dim3(64 * CP_ROWS), 0, s, a, params, T);
+  } else {
+    hipLaunchKernelGGL((conf_logits_kernel<512, false>), lgrid, dim3(CT_THREADS), 0, s, a, params, T);
+    if (trunc)
+      hipLaunchKernelGGL((conf_pick_kernel<true, false>), pgrid, dim3(64 * CP_ROWS), 0, s, a, params, T);
+    else
+      hipLaunchKernelGGL((conf_pick_kernel<false, false>), pgrid, dim3(64 * CP_ROWS), 0, s, a, params, T);
+  }
   T2H_CHECK_LAUNCH("t2h_confidence_tail");
   return T2H_OK;
 }
 
-extern "C" int t2h_confidence_commit(const t2h_confidence_commit_args* args, void* stream) {
+extern "C" int t2h_confidence_tail(const t2h_confidence_tail_args* args, void* stream) {
+  return confidence_tail_launch(args, nullptr, 0, stream);
+}
+
+extern "C" int t2h_confidence_tail_per_sample(const t2h_confidence_tail_args* args, const t2h_sample_params* params,
+                                              int32_t rows_per_sample, void* stream) {
+  T2H_REQUIRE(params != nullptr, "t2h_confidence_tail_per_sample: params is NULL");
+  return confidence_tail_launch(args, params, rows_per_sample, stream);
+}
+
+template <bool PER_SAMPLE>
+static int confidence_commit_launch(const t2h_confidence_commit_args* args, void* stream) {
   T2H_REQUIRE(args != nullptr, "t2h_confidence_commit: args is NULL");
   const t2h_confidence_commit_args a = *args;
   T2H_REQUIRE(a.conf && a.tok && a.tex && a.k && a.tau && a.x_t && a.out, "t2h_confidence_commit: NULL pointer");
@@ -1108,9 +1211,17 @@ extern "C" int t2h_confidence_commit(const t2h_confidence_commit_args* args, voi
               "t2h_confidence_commit: bad arguments (B=%d T=%d)", a.B, a.T);
   T2H_REQUIRE(a.u != nullptr || (a.philox_grid_threads != 0 && (a.philox_offset_dev || a.philox_offset % 4 == 0)),
               "t2h_confidence_commit: no noise (u, or philox_grid_threads and an offset that is a multiple of 4)");
-  hipLaunchKernelGGL(conf_commit_kernel, dim3(a.B), dim3(CC_THREADS), 0, static_cast<hipStream_t>(stream), a);
+  hipLaunchKernelGGL(conf_commit_kernel<PER_SAMPLE>, dim3(a.B), dim3(CC_THREADS), 0, static_cast<hipStream_t>(stream), a);
   T2H_CHECK_LAUNCH("t2h_confidence_commit");
   return T2H_OK;
+}
+
+extern "C" int t2h_confidence_commit(const t2h_confidence_commit_args* args, void* stream) {
+  return confidence_commit_launch<false>(args, stream);
+}
+
+extern "C" int t2h_confidence_commit_per_sample(const t2h_confidence_commit_args* args, void* stream) {
+  return confidence_commit_launch<true>(args, stream);
 }
 
 extern "C" int t2h_embed_sum4_f32(const int64_t* idx, const int64_t* segm, const int64_t* tex,
@@ -1156,9 +1267,13 @@ extern "C" int t2h_sample_head(const float* hidden, const float* lnf_gamma, cons
   return T2H_OK;
 }
 
-extern "C" int t2h_sample_heads(const t2h_sample_heads_args* args, void* stream) {
+// params == NULL: the launch's scalars (t2h_sample_heads); else the PER_SAMPLE instances (a.temp / a.top_k / a.top_p_q
+// are not read)
+static int sample_heads_launch(const t2h_sample_heads_args* args, const t2h_sample_params* params, int32_t T,
+                               void* stream) {
   T2H_REQUIRE(args != nullptr, "t2h_sample_heads: args is NULL");
   t2h_sample_heads_args a = *args;
+  if (params) a.temp = 1.f, a.top_k = 0, a.top_p_q = 0;
   T2H_REQUIRE(a.hidden && a.lnf_gamma && a.lnf_beta && a.w_heads && a.rows && a.tex && a.x_t && a.out_idx,
               "t2h_sample_heads: NULL pointer");
   T2H_REQUIRE(a.n > 0 && a.n_class > 0 && a.temp > 0.f && a.n_rows >= 0 && a.n_heads > 0 &&
@@ -1174,26 +1289,43 @@ extern "C" int t2h_sample_heads(const t2h_sample_heads_args* args, void* stream)
               "offsets, philox_grid_threads");
   T2H_TRUNC_REQUIRE("t2h_sample_heads", a.top_k, a.top_p_q, a.n_class);
   const bool trunc = trunc_settings(a.n_class, &a.top_k, &a.top_p_q);
+  if (params) T2H_PER_SAMPLE_REQUIRE("t2h_sample_heads_per_sample", params, T, a.n, a.n_class);
   if (a.n_rows == 0) return T2H_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
   if (a.logits_ws) {  // two launches, SL_SPLIT workgroups per row stream the head weights
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(sample_logits_kernel<512>, dim3(a.n_rows * SL_SPLIT), dim3(SL_THREADS), 0, s, a, a.logits_ws);
-    if (trunc)
-      hipLaunchKernelGGL(sample_pick_kernel<true>, dim3(a.n_rows), dim3(SH_THREADS), 0, s, a, a.logits_ws);
-    else
-      hipLaunchKernelGGL(sample_pick_kernel<false>, dim3(a.n_rows), dim3(SH_THREADS), 0, s, a, a.logits_ws);
+    const dim3 lgrid(a.n_rows * SL_SPLIT), pgrid(a.n_rows);
+    if (params) {
+      hipLaunchKernelGGL((sample_logits_kernel<512, true>), lgrid, dim3(SL_THREADS), 0, s, a, a.logits_ws, params, T);
+      hipLaunchKernelGGL((sample_pick_kernel<true, true>), pgrid, dim3(SH_THREADS), 0, s, a, a.logits_ws, params, T);
+    } else {
+      hipLaunchKernelGGL((sample_logits_kernel<512, false>), lgrid, dim3(SL_THREADS), 0, s, a, a.logits_ws, params, T);
+      if (trunc)
+        hipLaunchKernelGGL((sample_pick_kernel<true, false>), pgrid, dim3(SH_THREADS), 0, s, a, a.logits_ws, params, T);
+      else
+        hipLaunchKernelGGL((sample_pick_kernel<false, false>), pgrid, dim3(SH_THREADS), 0, s, a, a.logits_ws, params, T);
+    }
     T2H_CHECK_LAUNCH("t2h_sample_heads");
     return T2H_OK;
   }
   const size_t lds = (size_t)(a.n_class + 2 * (SH_THREADS / 64)) * sizeof(float);
-  if (trunc)
-    hipLaunchKernelGGL((sample_heads_kernel<512, true>), dim3(a.n_rows), dim3(SH_THREADS), lds,
-                       static_cast<hipStream_t>(stream), a);
+  if (params)
+    hipLaunchKernelGGL((sample_heads_kernel<512, true, true>), dim3(a.n_rows), dim3(SH_THREADS), lds, s, a, params, T);
+  else if (trunc)
+    hipLaunchKernelGGL((sample_heads_kernel<512, true, false>), dim3(a.n_rows), dim3(SH_THREADS), lds, s, a, params, T);
   else
-    hipLaunchKernelGGL((sample_heads_kernel<512, false>), dim3(a.n_rows), dim3(SH_THREADS), lds,
-                       static_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL((sample_heads_kernel<512, false, false>), dim3(a.n_rows), dim3(SH_THREADS), lds, s, a, params, T);
   T2H_CHECK_LAUNCH("t2h_sample_heads");
   return T2H_OK;
+}
+
+extern "C" int t2h_sample_heads(const t2h_sample_heads_args* args, void* stream) {
+  return sample_heads_launch(args, nullptr, 0, stream);
+}
+
+extern "C" int t2h_sample_heads_per_sample(const t2h_sample_heads_args* args, const t2h_sample_params* params,
+                                           int32_t rows_per_sample, void* stream) {
+  T2H_REQUIRE(params != nullptr, "t2h_sample_heads_per_sample: params is NULL");
+  return sample_heads_launch(args, params, rows_per_sample, stream);
 }
 
 extern "C" int t2h_q_sample(const int64_t* x0, const float* u, const int64_t* t, int32_t num_timesteps,

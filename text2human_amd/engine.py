@@ -8,13 +8,14 @@ and keeps activations as NHWC pixel rows [B*H*W, C] / token rows [B*T, C] in
 HBM.  PyTorch only allocates tensors and provides the stream.
 """
 import gc
+import numbers
 import os
 import weakref
 
 import numpy as np
 import torch
 
-from . import _lib, ops, schedule
+from . import _lib, ops, options, schedule
 from .ops import ACT_GELU, ACT_NONE, ACT_RELU, PRO_NONE, PRO_SWISH
 
 
@@ -690,22 +691,23 @@ def _schedule(tex_flat, tex_host, B, sample_steps, n_books, n_class, noise, comp
                           slots=to_dev(slot_of_row[p.order]), kept=kept)
 
 
-def _begin_run(net, tex_tok, n_books, noise, init, top_k, top_p):
-    """What both sampling loops do first -> (noise, n_class, trunc, tex_flat, tex_host); whatever raises here raises before
-    the generator has moved."""
+def _begin_run(net, tex_tok, n_books, noise, init, temp, top_k, top_p, per_image=False):
+    """What both sampling loops do first -> (noise, n_class, sp, tex_flat, tex_host); whatever raises here raises before
+    the generator has moved.  sp = ops.sampling_params: the scalar temp / truncation pair, or -- any of temp / top_k /
+    top_p given per image, or per_image set -- the table of the per-image tails (the caller's sample order)."""
+    n_class = net.P[f'{net.name}.heads'].shape[1]
+    sp = ops.sampling_params(tex_tok.shape[0], temp, top_k, top_p, n_class, per_image=per_image)
     if net.split:
         ops.split_overflow(reset=True)  # a flag left by an earlier stage is not this run's
         if net.x8:
             net.ensure_x8()  # calibration (an evaluation of its own; a no-op after a model's load) before the first round
             ops.split_overflow(reset=True)
-    n_class = net.P[f'{net.name}.heads'].shape[1]
-    trunc = ops.truncation_settings(top_k, top_p, n_class)
     tex_flat, tex_host = _texture_ids(tex_tok, n_books)
     n = tex_flat.numel()
     if init is not None and (tuple(init[0].shape) != (n_books, n) or tuple(init[1].shape) != (n, )):
         raise ValueError(f'init: source lists [{n_books}, {n}] and keep [{n}] expected, got '
                          f'{tuple(init[0].shape)} / {tuple(init[1].shape)}')
-    return noise or TorchDeviceNoise(tex_tok.device), n_class, trunc, tex_flat, tex_host
+    return noise or TorchDeviceNoise(tex_tok.device), n_class, sp, tex_flat, tex_host
 
 
 def _initial_state(init, tex_tok, n_books, mask_id, n_class, x_t=None, out=None):
@@ -721,7 +723,8 @@ def _initial_state(init, tex_tok, n_books, mask_id, n_class, x_t=None, out=None)
 
 def _round(net, x_t, out, segm_tok, tex_tok, rows, n_rows, noise, temp, logits_ws, trunc_kw, defer=True, active=None):
     """One round of the reference's loop: the transformer on x_t (defer: the last layer's tail on the listed rows only,
-    and only the first `active` samples), then the tokens of the first n_rows of `rows` drawn into x_t / out."""
+    and only the first `active` samples), then the tokens of the first n_rows of `rows` drawn into x_t / out.  temp /
+    trunc_kw: the scalar controls (_trunc_kw), or temp None and the per-image table (_per_image_kw)."""
     compact = False
     if defer:
         net.hidden(x_t, segm_tok, tex_tok, defer_tail=True, active=active)
@@ -741,14 +744,21 @@ class RoundGraph:
     round -- a power of two --, temperature) for every count of running samples, before the first run
     (prepare), replayed for every round of every run."""
 
-    def __init__(self, net, B, T, steps, maxr, n_books, n_class, temp, mask_id, dev, trunc=(0, 0)):
+    def __init__(self, net, B, T, steps, maxr, n_books, n_class, temp, mask_id, dev, trunc=(0, 0), per_image=False):
         i64 = lambda *s: torch.empty(s, dtype=torch.int64, device=dev)
         i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)
         # (a weak reference: net._graphs owns this object -- a strong one would make a cycle that only the cyclic
         # collector frees, at a moment of ITS choosing, e.g. in the middle of another graph's capture)
         self._net = weakref.ref(net)
-        self.maxr, self.temp, self.mask_id, self.n_class = maxr, float(temp), mask_id, n_class
-        self.trunc = _trunc_kw(trunc)  # (captured by value, like temp: part of the graph key)
+        self.maxr, self.mask_id, self.n_class = maxr, mask_id, n_class
+        if per_image:
+            # the table of the per-image tails: a persistent buffer the captured launches point to, filled by run()
+            # before the replays like rows_tbl -- its VALUES are not captured, so they are not part of the graph key
+            self.params = i32(B, 3)
+            self.temp, self.trunc = None, _per_image_kw(self.params, T)
+        else:
+            self.params, self.temp = None, float(temp)
+            self.trunc = _trunc_kw(trunc)  # (captured by value, like temp: part of the graph key)
         self.x_t, self.out, self.segm, self.tex = i64(B, T), i64(n_books, B * T), i64(B, T), i64(B, T)
         self.rows_tbl, self.offs_tbl, self.rng_tbl = i32(steps, maxr), i64(steps, maxr), i32(steps, maxr)
         self.cur_rows, self.cur_offs, self.cur_rng = i32(maxr), i64(maxr), i32(maxr)
@@ -796,10 +806,11 @@ class RoundGraph:
                 gc.enable()
         self.graphs[k] = g
 
-    def run(self, sched, segm_tok, tex_tok, init=None):
+    def run(self, sched, segm_tok, tex_tok, init=None, params=None):
         """All rounds of one run on this graph's stream; returns `out` (valid once the caller's stream
         has waited, which this does).  init = (src_lists, keep) in the schedule's sample order (region editing):
-        x_t / out start from t2h_edit_prefill instead of all-masked -- before the replays, outside any capture."""
+        x_t / out start from t2h_edit_prefill instead of all-masked -- before the replays, outside any capture.
+        params (a per-image graph): the run's table (ops.SAMPLE_PARAMS_DTYPE [B]) in the schedule's sample order."""
         order, offs, rng_rows = sched.host
         tables = schedule.RoundTables(order, offs, sched.start, self.maxr, per_row32=rng_rows if rng_rows is not None else order)
         R, rows_tbl, offs_tbl = tables.n_rounds, tables.rows_tbl, tables.val_tbl
@@ -808,6 +819,8 @@ class RoundGraph:
         self.stream.wait_stream(caller)
         with torch.cuda.stream(self.stream):
             ops.split_overflow(reset=True)  # (this stream's flag; allocated here, before any capture)
+            if self.params is not None:  # (before prepare: its eager round reads a valid table)
+                self.params.copy_(ops.sample_params_tensor(params, 'cpu'), non_blocking=False)
             counts = set(range(1, self.B + 1)) if sched.active is not None else {self.B}
             if not counts <= set(self.graphs):
                 self.prepare(counts)
@@ -835,6 +848,17 @@ def _trunc_kw(trunc):
     return dict(top_k=int(k), top_p=(int(p_q) / ops.TOP_P_ONE if p_q else 1.0))
 
 
+def _per_image_kw(params, T):
+    """the per-image table on the device (ops.sample_params_tensor) -> the keyword arguments of the tail launches"""
+    return dict(params=params, rows_per_sample=int(T))
+
+
+def round_graph_key_per_image(B, T, sample_steps, maxr, mask_id, n_books, x8):
+    """The key of the captured rounds of per-image runs: the table is read from a buffer of the graph, so neither
+    temperatures nor truncation settings are held by value -- runs with different values share the captures."""
+    return (B, T, sample_steps, maxr, int(mask_id), n_books, bool(x8), 'per-sample')
+
+
 def round_graph_key(B, T, sample_steps, maxr, temp, mask_id, n_books, x8, trunc=(0, 0)):
     """What a captured round (RoundGraph) holds BY VALUE: two calls share a graph iff this key is equal."""
     return (B, T, sample_steps, maxr, float(temp), int(mask_id), n_books, bool(x8), int(trunc[0]), int(trunc[1]))
@@ -859,6 +883,10 @@ def sample_tokens(net, segm_tok, tex_tok, sample_steps, mask_id, temp=1.0, noise
     top_k / top_p: truncated sampling ("Truncated sampling"; ops.truncation_settings): every token draw is
     restricted to the classes at or above the row's threshold.  The generator is consumed as without it.
 
+    temp / top_k / top_p may each be a sequence with one entry per image, in the caller's sample order (DESIGN.md,
+    "Per-image sampling controls"; ops.sampling_params): image b is then, bit for bit, image b of the call with
+    image b's values as scalars; the schedule and the generator do not depend on them.  Scalars take the scalar path.
+
     init = (src_lists int64 [n_books, B*T], keep uint8 [B*T]) -- region editing ("Editing a region"): the
     rows with keep != 0 start as their source token and are never resampled; everything else is the loop above, with
     the generator consumed exactly as the reference's loop started from that state would consume it.
@@ -872,7 +900,8 @@ def sample_tokens(net, segm_tok, tex_tok, sample_steps, mask_id, temp=1.0, noise
         compact = step_hook is None and os.environ.get('T2H_COMPACT_ROUNDS', '1') != '0'
     if compact and step_hook is not None:
         raise ValueError('step_hook needs compact=False (samples are at different steps in a compact round)')
-    noise, n_class, trunc, tex_flat, tex_host = _begin_run(net, tex_tok, n_books, noise, init, top_k, top_p)
+    noise, n_class, sp, tex_flat, tex_host = _begin_run(net, tex_tok, n_books, noise, init, temp, top_k, top_p)
+    table = sp.table
     # finished samples leave the batch (T2H_SHRINK_BATCH=0 opts out; hooks see the batch in its own order)
     shrink = (compact and step_hook is None and round_hook is None and os.environ.get('T2H_SHRINK_BATCH', '1') != '0')
     sched = _schedule(tex_flat, tex_host, B, sample_steps, n_books, n_class, noise, compact, shrink, init)
@@ -887,6 +916,8 @@ def sample_tokens(net, segm_tok, tex_tok, sample_steps, mask_id, temp=1.0, noise
         segm_tok, tex_tok = segm_tok[perm_t].contiguous(), tex_tok[perm_t].contiguous()
         if init is not None:  # the initial state in the schedule's sample order, like segm_tok / tex_tok
             init = (init[0].view(-1, B, T)[:, perm_t].reshape(-1, n).contiguous(), init[1].view(B, T)[perm_t].reshape(n))
+        if table is not None:  # the kernels index the table by the sample's position in the batch THEY see
+            table = table[sched.perm]
         caller_rows = torch.from_numpy(schedule.in_caller_order(sched.perm, B, T)).to(dev)
         in_batch_order = lambda out: out[:, caller_rows]
 
@@ -902,17 +933,22 @@ def sample_tokens(net, segm_tok, tex_tok, sample_steps, mask_id, temp=1.0, noise
         # padded rows per round: a power of two >= 16 (at most five graph sets per batch size, whatever the seeds)
         maxr = min(net.TRIM_MAX_ROWS, max(16, 1 << (int(sched.max_rows) - 1).bit_length()))
         net._buffers(n, net.desc['C'], dev)  # (a change of batch size drops the graphs of the old buffers)
-        key = round_graph_key(B, T, sample_steps, maxr, temp, mask_id, n_books, net.x8, trunc)
+        if table is None:
+            key = round_graph_key(B, T, sample_steps, maxr, temp, mask_id, n_books, net.x8, sp.trunc)
+        else:
+            key = round_graph_key_per_image(B, T, sample_steps, maxr, mask_id, n_books, net.x8)
         if key not in net._graphs:
-            net._graphs[key] = RoundGraph(net, B, T, sample_steps, maxr, n_books, n_class, temp, mask_id, dev, trunc=trunc)
-        return in_batch_order(net._graphs[key].run(sched, segm_tok, tex_tok, init=init).clone())
+            net._graphs[key] = RoundGraph(net, B, T, sample_steps, maxr, n_books, n_class, temp, mask_id, dev,
+                                          trunc=sp.trunc, per_image=table is not None)
+        return in_batch_order(net._graphs[key].run(sched, segm_tok, tex_tok, init=init, params=table).clone())
+    tail_kw = _trunc_kw(sp.trunc) if table is None else _per_image_kw(ops.sample_params_tensor(table, dev), T)
     x_t, out, _ = _initial_state(init, tex_tok, n_books, mask_id, n_class)
     logits_ws = torch.empty((max(sched.max_rows, 1), n_class), dtype=torch.float32, device=dev)
     for r in range(sched.n_rounds):
         lo, hi = int(sched.start[r]), int(sched.start[r + 1])
         k = int(sched.active[r]) if sched.active is not None else None
-        _round(net, x_t, out, segm_tok, tex_tok, sched.rows[lo:hi], hi - lo, sched.row_noise(lo, hi), temp, logits_ws,
-               _trunc_kw(trunc), defer, k)
+        _round(net, x_t, out, segm_tok, tex_tok, sched.rows[lo:hi], hi - lo, sched.row_noise(lo, hi), sp.temp, logits_ws,
+               tail_kw, defer, k)
         if round_hook is not None:
             round_hook(r, sched.round_steps[r], x_t, out)
         if step_hook is not None:
@@ -936,16 +972,37 @@ def sample_tokens_confidence(net, segm_tok, tex_tok, mask_id, rounds=16, temp=1.
     init = (src_lists, keep) as in sample_tokens.  top_k / top_p: truncated sampling as in sample_tokens -- it changes
     the token a row draws, never its confidence (the log-probability under the full softmax).  round_hook(r, x_t, out, tokens, conf, scores) is called after round
     r = 1 .. R and may overwrite x_t / out in place (teacher forcing); rounds after the last masked row of the whole
-    batch are not evaluated (their draws are still counted).  Returns int64 [n_books, B*T] (-1 off-texture)."""
+    batch are not evaluated (their draws are still counted).  Returns int64 [n_books, B*T] (-1 off-texture).
+
+    rounds / choice_temp / temp / top_k / top_p may each be a sequence with one entry per image ("Per-image
+    sampling controls"): the run has R = max rounds rounds and consumes the generator as the scalar call with R rounds;
+    image b commits in rounds 1 .. rounds[b] on schedule.confidence_schedule(M0_b, rounds[b]) with tau_{b,r} =
+    choice_temp[b] (1 - r / rounds[b]) and is, bit for bit, image b of the call with its values as scalars."""
     B, T = segm_tok.shape
     dev, n = segm_tok.device, B * T
-    R = int(rounds)
-    if R < 1:
-        raise ValueError(f'rounds must be >= 1, got {rounds}')
-    if not float(choice_temp) >= 0.0:
-        raise ValueError(f'choice_temp must be >= 0, got {choice_temp}')
-    noise, n_class, trunc, tex_flat, _ = _begin_run(net, tex_tok, n_books, noise, init, top_k, top_p)
-    trunc_kw = _trunc_kw(trunc)
+    rounds_b, ct_b = options.per_image_values(B, rounds, 'rounds'), options.per_image_values(B, choice_temp, 'choice_temp')
+    per_image = rounds_b is not None or ct_b is not None
+    if per_image:
+        rounds_b = [int(rounds)] * B if rounds_b is None else rounds_b
+        ct_b = [float(choice_temp)] * B if ct_b is None else ct_b
+        for b in range(B):
+            if isinstance(rounds_b[b], bool) or not isinstance(rounds_b[b], numbers.Integral) or int(rounds_b[b]) < 1:
+                raise ValueError(f'image {b}: rounds must be an integer >= 1, got {rounds_b[b]!r}')
+            if isinstance(ct_b[b], bool) or not isinstance(ct_b[b], numbers.Real) or not float(ct_b[b]) >= 0.0:
+                raise ValueError(f'image {b}: choice_temp must be >= 0, got {ct_b[b]!r}')
+        R = max(int(r) for r in rounds_b)
+    else:
+        R = int(rounds)
+        if R < 1:
+            raise ValueError(f'rounds must be >= 1, got {rounds}')
+        if not float(choice_temp) >= 0.0:
+            raise ValueError(f'choice_temp must be >= 0, got {choice_temp}')
+    noise, n_class, sp, tex_flat, _ = _begin_run(net, tex_tok, n_books, noise, init, temp, top_k, top_p, per_image)
+    per_image = sp.table is not None
+    if per_image and rounds_b is None:
+        rounds_b, ct_b = [R] * B, [choice_temp] * B
+    # (no reordering in this loop: the table is in the batch's own order)
+    trunc_kw = _per_image_kw(ops.sample_params_tensor(sp.table, dev), T) if per_image else _trunc_kw(sp.trunc)
     x_t, out, err = _initial_state(init, tex_flat.view(B, T), n_books, mask_id, n_class)
     m0 = np.full(B, T, dtype=np.int64)
     if init is not None:
@@ -954,11 +1011,14 @@ def sample_tokens_confidence(net, segm_tok, tex_tok, mask_id, rounds=16, temp=1.
     # the run's tables [R][w]: rows channel = k_r of every sample, 64-bit channel = generator offsets of the round's
     # exponential_ / rand draws, 32-bit channel = the bits of tau_r
     w = max(B, 2)
-    k_tbl = np.zeros((R, w), dtype=np.int32)
-    for b in range(B):
-        k_tbl[:, b] = schedule.confidence_schedule(int(m0[b]), R)[1]
-    tau_tbl = np.zeros((R, w), dtype=np.float32)
-    tau_tbl[:, 0] = schedule.confidence_choice_temps(R, choice_temp)
+    if per_image:
+        k_tbl, tau_tbl = schedule.confidence_tables(m0, rounds_b, ct_b, w)
+    else:
+        k_tbl = np.zeros((R, w), dtype=np.int32)
+        for b in range(B):
+            k_tbl[:, b] = schedule.confidence_schedule(int(m0[b]), R)[1]
+        tau_tbl = np.zeros((R, w), dtype=np.float32)
+        tau_tbl[:, 0] = schedule.confidence_choice_temps(R, choice_temp)
     off_tbl = np.zeros((R, w), dtype=np.int64)
     philox = isinstance(noise, TorchDeviceNoise) and noise.emulation_ok(n, n_class)
     seed = None
@@ -995,10 +1055,10 @@ def sample_tokens_confidence(net, segm_tok, tex_tok, mask_id, rounds=16, temp=1.
             noise_e = ('explicit', noise.exponential(r, None, (n, n_class)).to(dev, torch.float32).contiguous())
             noise_u = ('explicit', noise.uniform(r, (n, )).to(dev, torch.float32).reshape(-1).contiguous())
         hidden = net.hidden(x_t, segm_tok, tex_tok)
-        ops.confidence_tail(hidden, lnf_g, lnf_b, heads, tex_flat, x_t.view(-1), mask_id, temp, noise_e, tok, conf,
+        ops.confidence_tail(hidden, lnf_g, lnf_b, heads, tex_flat, x_t.view(-1), mask_id, sp.temp, noise_e, tok, conf,
                             group_ws=group_ws, logits_ws=logits_ws, **trunc_kw)
         ops.confidence_commit(conf, tok, tex_flat, noise_u, cur_k, cur_tau.view(torch.float32), mask_id, x_t, out,
-                              n_class, scores=scores)
+                              n_class, scores=scores, per_sample=per_image)
         if round_hook is not None:
             round_hook(r, x_t, out, tok, conf, scores)
     if not philox:  # the draws of the rounds that were not evaluated

@@ -110,14 +110,23 @@ class BaseSampleModel():
     def sample_fn(self, temp=1.0, sample_steps=None, top_k=None, top_p=None):
         """models/sample_model.py:256-328 -> list of 18 int64 [B, 512].  top_k / top_p (not in the reference; DESIGN.md
         "Truncated sampling"): every draw only among the k most likely classes / the smallest set of most likely classes
-        holding top_p of the probability.  None = off = the reference's draw."""
+        holding top_p of the probability.  None = off = the reference's draw.  temp / top_k / top_p may each be a
+        sequence with one entry per image of the batch (DESIGN.md "Per-image sampling controls"): image b is then the
+        image b of the call with its own values as scalars."""
         return self._sample(temp, sample_steps or self.sample_steps, top_k=top_k, top_p=top_p)
 
     @torch.no_grad()
     def sample_fn_confidence(self, rounds=16, temp=1.0, choice_temp=4.5, top_k=None, top_p=None):
         """Confidence-ordered parallel decoding (opt-in; DESIGN.md "Confidence-ordered decoding"): all tokens in
-        `rounds` transformer evaluations instead of one per active step -> list of 18 int64 [B, 512] like sample_fn."""
-        return self._sample(temp, None, confidence=(int(rounds), float(choice_temp)), top_k=top_k, top_p=top_p)
+        `rounds` transformer evaluations instead of one per active step -> list of 18 int64 [B, 512] like sample_fn.
+        rounds / choice_temp / temp / top_k / top_p may each be a sequence with one entry per image."""
+        return self._sample(temp, None, confidence=self._confidence_args(rounds, choice_temp), top_k=top_k, top_p=top_p)
+
+    @staticmethod
+    def _confidence_args(rounds, choice_temp):
+        """(rounds, choice_temp) for _sample: scalars as int / float, per-image sequences as they are"""
+        return (rounds if options.is_per_image(rounds) else int(rounds),
+                choice_temp if options.is_per_image(choice_temp) else float(choice_temp))
 
     def _confidence_options(self):
         """(rounds, choice_temp) if the options select `sample_order: confidence`, else None (the reference's loop)."""
@@ -131,7 +140,7 @@ class BaseSampleModel():
         """sample_fn's body (init: engine.sample_tokens' initial state of a region edit; confidence = (rounds,
         choice_temp): engine.sample_tokens_confidence instead of the reference's loop; top_k / top_p: truncated
         sampling, passed to every attempt of the fall-back chain below)."""
-        ops.truncation_settings(top_k, top_p)  # (raises before anything is evaluated or drawn)
+        ops.sampling_params(self.batch_size, temp, top_k, top_p)  # (raises before anything is evaluated or drawn)
         tex_tok = self._texture_tokens(self.texture_mask)
         # The reference computes ANY checkpoint in fp32 (transformer_arch.py:91-99).  The split-precision kernels
         # cover |x| < 65504; an activation outside raises SplitOverflowError at the end of the run -- after
@@ -218,17 +227,20 @@ class BaseSampleModel():
         sample_fn's format.  A kept row must have an index under the CURRENT texture map (T2HError otherwise; nothing
         changes).  order='confidence': the masked rows are filled by confidence-ordered decoding in `rounds` (default
         16) rounds, every sample on the schedule of its own number of resampled rows.  top_k / top_p: truncated
-        sampling of the resampled rows, as in sample_fn."""
+        sampling of the resampled rows, as in sample_fn.  temp / top_k / top_p / rounds / choice_temp may each be a
+        sequence with one entry per image, as in sample_fn / sample_fn_confidence."""
         if order not in ('random', 'confidence'):
             raise ValueError(f"order must be 'random' or 'confidence', got {order!r}")
         init = (self._token_lists(top_indices_list, 'resample_fn'), self._keep_rows(keep))
-        confidence = (int(rounds or 16), float(choice_temp)) if order == 'confidence' else None
+        if not options.is_per_image(rounds):
+            rounds = int(rounds or 16)
+        confidence = self._confidence_args(rounds, choice_temp) if order == 'confidence' else None
         return self._sample(temp, sample_steps or self.sample_steps, init=init, confidence=confidence, top_k=top_k,
                             top_p=top_p)
 
     @torch.no_grad()
     def edit_and_refine(self, top_indices_list, region=None, labels=None, bot_indices_list=None, save_dir=None,
-                        img_name=None, order='random', rounds=None, choice_temp=4.5, top_k=None, top_p=None):
+                        img_name=None, order='random', rounds=None, choice_temp=4.5, top_k=None, top_p=None, temp=1.0):
         """Region edit end to end: resample the top tokens of the region (region_keep), predict the bottom indices,
         keep `bot_indices_list` (e.g. a photo's bot_encode) outside the region if given, decode.  Return values and
         files follow sample_and_refine: with save_dir and img_name both None the first image f32 [1, 3, H, W];
@@ -242,7 +254,7 @@ class BaseSampleModel():
             tex = self._texture_tokens(self.texture_mask).reshape(-1)
             err = ops.edit_prefill(bot, tex, keep_rows, 0, self.P['bot.books'].shape[1])  # (check only)
             engine._init_check(err, keep_rows, self.shape[0] * self.shape[1])
-        top = self.resample_fn(top_indices_list, keep, order=order, rounds=rounds, choice_temp=choice_temp,
+        top = self.resample_fn(top_indices_list, keep, temp=temp, order=order, rounds=rounds, choice_temp=choice_temp,
                                top_k=top_k, top_p=top_p)
         want_files = not (save_dir is None and img_name is None)
         bot_keep = (bot, keep_rows) if bot is not None else None

@@ -6,8 +6,10 @@ the current HIP stream, and calls into libt2h_hip.so.
 """
 import collections
 import ctypes
+import numbers
 import os
 
+import numpy as np
 import torch
 
 from . import _lib, options
@@ -871,6 +873,67 @@ TOP_P_ONE = options.TOP_P_ONE
 truncation_settings = options.truncation_settings
 
 
+# ---- per-image sampling controls ("Per-image sampling controls")
+SAMPLE_PARAMS_DTYPE = np.dtype([('temp', '<f4'), ('top_k', '<i4'), ('top_p_q', '<u4')])  # struct t2h_sample_params
+assert SAMPLE_PARAMS_DTYPE.itemsize == ctypes.sizeof(_lib.SampleParams) == 12
+
+# scalar controls: temp as given, trunc = truncation_settings' pair, table None (today's launches); per image: table =
+# SAMPLE_PARAMS_DTYPE [B] in the CALLER's sample order (the engine permutes it with the batch), temp / trunc None
+SamplingParams = collections.namedtuple('SamplingParams', 'temp trunc table')
+
+
+def sampling_params(batch, temp=1.0, top_k=None, top_p=None, n_class=None, per_image=False):
+    """The draw controls of one sampling call, validated on the host (ValueError; nothing has been drawn or launched):
+    all scalars -> SamplingParams(temp, truncation_settings(top_k, top_p, n_class), None), exactly what the scalar
+    path always used.  If any of the three is a sequence with one entry per image (options.per_image_values), or
+    per_image is set (a per-image control of another kind: rounds, choice_temp), -> the table of t2h_sample_params,
+    scalars repeated for every image.  Entry b must be what the scalar accepts (temp > 0; truncation_settings); an
+    error names the image.  A sequence whose entries are all equal stays a table."""
+    seqs = [options.per_image_values(batch, v, what) for v, what in ((temp, 'temp'), (top_k, 'top_k'), (top_p, 'top_p'))]
+    if all(s is None for s in seqs) and not per_image:
+        return SamplingParams(temp, truncation_settings(top_k, top_p, n_class), None)
+    temps, ks, ps = (s if s is not None else [v] * int(batch) for s, v in zip(seqs, (temp, top_k, top_p)))
+    table = np.zeros(int(batch), dtype=SAMPLE_PARAMS_DTYPE)
+    for b in range(int(batch)):
+        t = temps[b]
+        if isinstance(t, bool) or not isinstance(t, numbers.Real) or not float(t) > 0.0 or float(t) == float('inf'):
+            raise ValueError(f'image {b}: temp must be a finite number > 0, got {t!r}')
+        try:
+            k, p_q = truncation_settings(ks[b], ps[b], n_class)
+        except ValueError as e:
+            raise ValueError(f'image {b}: {e}') from None
+        table[b] = (float(t), k, p_q)
+    return SamplingParams(None, None, table)
+
+
+def sample_params_tensor(table, device):
+    """SAMPLE_PARAMS_DTYPE [B] (host) -> int32 [B, 3] on the device: the bytes of t2h_sample_params[B]"""
+    assert table.dtype == SAMPLE_PARAMS_DTYPE and table.ndim == 1
+    return torch.from_numpy(np.ascontiguousarray(table).view(np.int32).reshape(-1, 3).copy()).to(device)
+
+
+def _chk_params(params, rows_per_sample, n):
+    """a device table for the *_per_sample entry points: int32 [B, 3] with B * rows_per_sample == n"""
+    T = int(rows_per_sample)
+    assert params.dtype == torch.int32 and params.is_cuda and params.is_contiguous() and params.dim() == 2
+    assert params.shape[1] == 3 and T > 0 and params.shape[0] * T == n, (tuple(params.shape), T, n)
+    return T
+
+
+def truncation_threshold_per_row(logits, params, rows_per_sample, scope=0):
+    """truncation_threshold with row r's rules taken from params[r // rows_per_sample] (sample_params_tensor;
+    t2h_truncation_threshold_per_row) -> theta f32 [n_rows], kept int32 [n_rows]"""
+    _chk_f32(logits)
+    assert logits.dim() == 2 and logits.is_contiguous()
+    n_rows, n_class = logits.shape
+    T = _chk_params(params, rows_per_sample, n_rows)
+    theta = torch.empty(n_rows, dtype=torch.float32, device=logits.device)
+    kept = torch.empty(n_rows, dtype=torch.int32, device=logits.device)
+    check(_lib.load().t2h_truncation_threshold_per_row(_p(logits), n_rows, n_class, _p(params), T, int(scope), _p(theta),
+                                                       _p(kept), _stream()), 't2h_truncation_threshold_per_row')
+    return theta, kept
+
+
 def truncation_threshold(logits, top_k=None, top_p=None, scope=0):
     """The row thresholds of truncated sampling by themselves (t2h_truncation_threshold): logits f32 [n_rows, n_class]
     (already divided by the temperature) -> theta f32 [n_rows], kept int32 [n_rows].  scope 0 / 1: the workgroup /
@@ -898,7 +961,8 @@ def _philox_fields(a, numel, device, **fields):
 
 
 def sample_heads(hidden, lnf_g, lnf_b, w_heads, expo_by_head, rows, n_rows, tex, temp, x_t, out_idx, split=True,
-                 philox=None, hidden_compact=False, row_noise=None, logits_ws=None, top_k=0, top_p=1.0):
+                 philox=None, hidden_compact=False, row_noise=None, logits_ws=None, top_k=0, top_p=1.0, params=None,
+                 rows_per_sample=None):
     """All heads in one launch: `rows` (int32, first n_rows valid) are the changed token
     rows, expo_by_head {head: [n, n_class] Exp(1) draw}, w_heads [n_heads, n_class, C],
     out_idx [n_heads, n].  philox = (seed, {head: generator offset}): the noise of the listed heads is
@@ -907,9 +971,11 @@ def sample_heads(hidden, lnf_g, lnf_b, w_heads, expo_by_head, rows, n_rows, tex,
     ('philox', seed, offsets int64 [>= n_rows][, rng_rows int32 [>= n_rows]]) = per-listed-row generator offsets (and
     the rows of the reference's draw they belong to, if the samples were reordered), or
     ('explicit', expo_rows f32 [*, n_class], slots int32 [>= n_rows]) = per-listed-row explicit draws.
-    top_k / top_p: truncated sampling (truncation_settings; the defaults are off = the kernels without it)."""
+    top_k / top_p: truncated sampling (truncation_settings; the defaults are off = the kernels without it).
+    params (sample_params_tensor) + rows_per_sample: per-image controls (t2h_sample_heads_per_sample) -- row r is drawn
+    with params[r // rows_per_sample]; temp / top_k / top_p are then not read."""
     _chk_f32(hidden, lnf_g, lnf_b, w_heads, *expo_by_head.values())
-    trunc = truncation_settings(top_k, top_p, w_heads.shape[1])
+    trunc = truncation_settings(top_k, top_p, w_heads.shape[1]) if params is None else (0, 0)
     if int(n_rows) == 0:
         return
     C = hidden.shape[1]
@@ -924,7 +990,7 @@ def sample_heads(hidden, lnf_g, lnf_b, w_heads, expo_by_head, rows, n_rows, tex,
         assert e.shape == (n, n_class) and e.is_contiguous()
         a.expo[h] = e.data_ptr()
     a.rows, a.tex, a.x_t, a.out_idx = rows.data_ptr(), tex.data_ptr(), x_t.data_ptr(), out_idx.data_ptr()
-    a.temp, a.n_rows, a.n, a.C, a.n_class, a.n_heads = float(temp), int(n_rows), n, C, n_class, n_heads
+    a.temp, a.n_rows, a.n, a.C, a.n_class, a.n_heads = (float(temp) if params is None else 1.0), int(n_rows), n, C, n_class, n_heads
     a.hidden_compact = int(bool(hidden_compact))
     a.top_k, a.top_p_q = trunc
     if (split or philox is not None or hidden_compact or row_noise is not None) and n_rows > 0:
@@ -953,6 +1019,10 @@ def sample_heads(hidden, lnf_g, lnf_b, w_heads, expo_by_head, rows, n_rows, tex,
         _philox_fields(a, n * n_class, hidden.device, philox_seed=philox[0])
         for h, off in philox[1].items():
             a.philox_offset[h] = int(off)
+    if params is not None:
+        T = _chk_params(params, rows_per_sample, n)
+        return check(_lib.load().t2h_sample_heads_per_sample(ctypes.byref(a), _p(params), T, _stream()),
+                     't2h_sample_heads_per_sample')
     check(_lib.load().t2h_sample_heads(ctypes.byref(a), _stream()), 't2h_sample_heads')
 
 
@@ -963,12 +1033,13 @@ def confidence_group_ws(n, n_heads, device):
 
 
 def confidence_tail(hidden, lnf_g, lnf_b, w_heads, tex, x_t, mask_id, temp, noise, tok, conf, group_ws=None,
-                    logits_ws=None, top_k=0, top_p=1.0):
+                    logits_ws=None, top_k=0, top_p=1.0, params=None, rows_per_sample=None):
     """Token and confidence of EVERY masked row (t2h_confidence_tail): hidden f32 [n, C], w_heads [n_heads, n_class, C],
     tex / x_t int64 [n] -> tok int32 [n] (-1 where not masked), conf f32 [n] (-inf where not masked).  noise:
     ('explicit', E f32 [n, n_class]) or ('philox', seed, offset) = the elements of torch's
     `empty(n, n_class).exponential_()` at that generator state.  top_k / top_p: truncated sampling
-    (truncation_settings) -- changes tok only, conf stays the log-probability under the full softmax."""
+    (truncation_settings) -- changes tok only, conf stays the log-probability under the full softmax.  params +
+    rows_per_sample: per-image controls as in sample_heads (t2h_confidence_tail_per_sample)."""
     _chk_f32(hidden, lnf_g, lnf_b, w_heads, conf)
     _chk_i64(tex, x_t)
     n, C = hidden.shape
@@ -982,9 +1053,9 @@ def confidence_tail(hidden, lnf_g, lnf_b, w_heads, tex, x_t, mask_id, temp, nois
     assert group_ws.numel() >= int(_lib.load().t2h_confidence_group_ws_ints(n, n_heads))
     a = _lib.ConfidenceTailArgs()
     a.hidden, a.lnf_gamma, a.lnf_beta, a.w_heads = hidden.data_ptr(), lnf_g.data_ptr(), lnf_b.data_ptr(), w_heads.data_ptr()
-    a.tex, a.x_t, a.mask_id, a.temp = tex.data_ptr(), x_t.data_ptr(), int(mask_id), float(temp)
+    a.tex, a.x_t, a.mask_id, a.temp = tex.data_ptr(), x_t.data_ptr(), int(mask_id), (float(temp) if params is None else 1.0)
     a.n, a.C, a.n_class, a.n_heads = n, C, n_class, n_heads
-    a.top_k, a.top_p_q = truncation_settings(top_k, top_p, n_class)
+    a.top_k, a.top_p_q = truncation_settings(top_k, top_p, n_class) if params is None else (0, 0)
     if noise[0] == 'explicit':
         e = noise[1]
         _chk_f32(e)
@@ -993,21 +1064,28 @@ def confidence_tail(hidden, lnf_g, lnf_b, w_heads, tex, x_t, mask_id, temp, nois
     else:
         _philox_fields(a, n * n_class, dev, philox_seed=noise[1], philox_offset=noise[2])
     a.group_ws, a.logits_ws, a.tok, a.conf = group_ws.data_ptr(), logits_ws.data_ptr(), tok.data_ptr(), conf.data_ptr()
+    if params is not None:
+        T = _chk_params(params, rows_per_sample, n)
+        check(_lib.load().t2h_confidence_tail_per_sample(ctypes.byref(a), _p(params), T, _stream()),
+              't2h_confidence_tail_per_sample')
+        return tok, conf
     check(_lib.load().t2h_confidence_tail(ctypes.byref(a), _stream()), 't2h_confidence_tail')
     return tok, conf
 
 
-def confidence_commit(conf, tok, tex, noise, k, tau, mask_id, x_t, out, n_class, scores=None):
+def confidence_commit(conf, tok, tex, noise, k, tau, mask_id, x_t, out, n_class, scores=None, per_sample=False):
     """Commits, per sample, the k[b] masked rows with the largest score conf + tau * gumbel(U) (t2h_confidence_commit):
     x_t int64 [B, T] and out int64 [n_heads, B * T] are updated in place.  k int32 [>= B] and tau f32 [>= 1] are device
-    tensors; noise: ('explicit', U f32 [B * T]) or ('philox', seed, offset) = the elements of torch's `rand(B * T)`."""
+    tensors; noise: ('explicit', U f32 [B * T]) or ('philox', seed, offset) = the elements of torch's `rand(B * T)`.
+    per_sample: tau is f32 [>= B], sample b scores with tau[b] (t2h_confidence_commit_per_sample)."""
     _chk_f32(conf, tau)
     _chk_i64(tex, x_t, out)
     B, T = x_t.shape
     n = B * T
     n_heads = out.shape[0]
     assert tuple(out.shape) == (n_heads, n) and conf.numel() == n and tok.numel() == n and tex.numel() == n
-    assert tok.dtype == torch.int32 and k.dtype == torch.int32 and k.is_cuda and k.numel() >= B and tau.numel() >= 1
+    assert tok.dtype == torch.int32 and k.dtype == torch.int32 and k.is_cuda and k.numel() >= B
+    assert tau.numel() >= (B if per_sample else 1)
     a = _lib.ConfidenceCommitArgs()
     a.conf, a.tok, a.tex = conf.data_ptr(), tok.data_ptr(), tex.data_ptr()
     if noise[0] == 'explicit':
@@ -1023,6 +1101,9 @@ def confidence_commit(conf, tok, tex, noise, k, tau, mask_id, x_t, out, n_class,
         assert scores.numel() == n
         a.scores = scores.data_ptr()
     a.B, a.T, a.n_heads, a.n_class = B, T, n_heads, int(n_class)
+    if per_sample:
+        return check(_lib.load().t2h_confidence_commit_per_sample(ctypes.byref(a), _stream()),
+                     't2h_confidence_commit_per_sample')
     check(_lib.load().t2h_confidence_commit(ctypes.byref(a), _stream()), 't2h_confidence_commit')
 
 

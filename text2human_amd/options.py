@@ -127,6 +127,28 @@ def truncation_settings(top_k=None, top_p=None, n_class=None):
     return k, p_q
 
 
+def per_image_values(batch, value, what):
+    """A sampling control given PER IMAGE ("Per-image sampling controls") -> the list of its `batch` entries
+    as plain Python values, in the caller's sample order; None if `value` is what it always could be (a scalar or
+    None).  Per image = a list, a tuple, a 1-D numpy array or a 1-D CPU tensor; a wrong length is a ValueError."""
+    if isinstance(value, (list, tuple)):
+        vals = list(value)
+    elif getattr(value, 'ndim', 0) >= 1 and hasattr(value, 'tolist'):
+        if value.ndim != 1:
+            raise ValueError(f'{what}: one entry per image expected (a 1-D sequence), got shape {tuple(value.shape)}')
+        vals = list(value.tolist())
+    else:
+        return None
+    if len(vals) != int(batch):
+        raise ValueError(f'{what}: one entry per image expected, got {len(vals)} entries for a batch of {int(batch)}')
+    return vals
+
+
+def is_per_image(value):
+    """True iff `value` is a per-image sequence (per_image_values), whatever its length"""
+    return isinstance(value, (list, tuple)) or (getattr(value, 'ndim', 0) >= 1 and hasattr(value, 'tolist'))
+
+
 def sampling_truncation(opt):
     """-> (top_k, top_p) of the options `sample_top_k` / `sample_top_p` (None where absent), validated."""
     top_k, top_p = opt.get('sample_top_k'), opt.get('sample_top_p')

@@ -229,6 +229,23 @@ def confidence_choice_temps(rounds, choice_temp):
     return (np.float64(choice_temp) * (1.0 - r / np.float64(R))).astype(np.float32)
 
 
+def confidence_tables(m0, rounds, choice_temps, width=None):
+    """Per-image confidence schedules ("Per-image sampling controls") as the [R][width] tables
+    t2h_schedule_advance walks, R = max rounds: column b of k = confidence_schedule(m0[b], rounds[b])'s commits in rows
+    0 .. rounds[b] - 1 and zero below -- image b is complete after its own last round --, column b of tau =
+    confidence_choice_temps(rounds[b], choice_temps[b]), zero below.  -> (k int32 [R, width], tau float32 [R, width])"""
+    B = len(m0)
+    if not (len(rounds) == len(choice_temps) == B):
+        raise ValueError(f'confidence_tables: {B} images, {len(rounds)} rounds, {len(choice_temps)} choice temperatures')
+    R = max(int(r) for r in rounds)
+    w = max(B, 2) if width is None else int(width)
+    k_tbl, tau_tbl = np.zeros((R, w), dtype=np.int32), np.zeros((R, w), dtype=np.float32)
+    for b in range(B):
+        k_tbl[:int(rounds[b]), b] = confidence_schedule(int(m0[b]), rounds[b])[1]
+        tau_tbl[:int(rounds[b]), b] = confidence_choice_temps(rounds[b], choice_temps[b])
+    return k_tbl, tau_tbl
+
+
 def stats(round_steps, steps, active=None, kept=None):
     """Evaluation counts for the bench line: (sample, step) pairs the reference evaluates, pairs that
     change a token (the ones whose logits are read), rounds launched, and the (sample, round) pairs the
