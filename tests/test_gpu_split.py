@@ -6,6 +6,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from split_ref import pack_vt_host as _pack_vt_host
 from text2human_amd import _lib, engine, ops, synthetic, weights
 
 pytestmark = pytest.mark.gpu
@@ -85,15 +86,6 @@ def test_sampler_net_split_matches_oracle_and_fp32_path():
     ea, eb = (ln(a) - ref).abs().max().item(), (ln(b) - ref).abs().max().item()
     assert ea < 1e-4 and eb < 1e-4, (ea, eb)
     assert eb < 3 * ea + 1e-6, f'split path error {eb:.2e} vs fp32 path {ea:.2e}'
-
-
-def _pack_vt_host(v, B, T, H):
-    """fp32 v [B*T, H*64] -> Vt [B][H][2][64][T] (int16 view) in the kernel's key order"""
-    vt = v.view(B, T, H, 64).permute(0, 2, 3, 1).contiguous()          # [B, H, 64, T]
-    pl = torch.stack(ops.split_planes_host(vt)).permute(1, 2, 0, 3, 4).contiguous()  # [B, H, 2, 64, T]
-    out = torch.empty_like(pl)
-    out[..., ops.vt_key_positions(T)] = pl
-    return out.view(torch.int16)
 
 
 @pytest.mark.parametrize('cfg', [-1, 0, 2, 3, 6, 8, 10])

@@ -7,6 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from split_ref import e4m3 as _e4m3, emulate_x8 as _emulate, x8_planes_host as _x8_planes_host
 from text2human_amd import _lib, engine, ops, synthetic, weights
 
 pytestmark = pytest.mark.gpu
@@ -15,23 +16,6 @@ DEV = 'cuda'
 
 def _rnd(*shape, seed=0, scale=1.0):
     return torch.randn(*shape, generator=torch.Generator().manual_seed(seed)) * scale
-
-
-def _e4m3(x):
-    return x.clamp(-448.0, 448.0).to(torch.float8_e4m3fn).float()
-
-
-def _x8_planes_host(x, s):
-    """(hi, h8, l8) as the numbers they stand for: hi = fp16(x), h8 = e4m3(hi s) / s, l8 = e4m3((x - hi) 2048 s) / s"""
-    hi = x.half().float()
-    return hi, _e4m3(hi * s) / s, _e4m3((x - hi) * 2048.0 * s) / s
-
-
-def _emulate(a, w, sa, sw):
-    """the kernel's arithmetic in fp64: ah.bh + (ah8.bl8 + al8.bh8) / 2048"""
-    ah, ah8, al8 = [t.double() for t in _x8_planes_host(a, sa)]
-    bh, bh8, bl8 = [t.double() for t in _x8_planes_host(w, sw)]
-    return ah @ bh.t() + (ah8 @ bl8.t() + al8 @ bh8.t()) / 2048.0
 
 
 def test_split_rows_x8_planes_and_range_bits():
