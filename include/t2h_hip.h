@@ -575,6 +575,46 @@ int t2h_routed_head_argmax(const float* feat, int32_t ldf, const float* w,
                            int32_t n, int32_t n_heads, int32_t Cf, int32_t n_class,
                            void* stream);
 
+/* Sampled bottom-index refinement (opt-in, not in the reference): the same routed 1x1 head, but the
+ * detail code of a token is DRAWN from the head's softmax instead of being its mode.  For token row r, t = tex[r]:
+ *   raw_j = (fma chain over k = 0 .. Cf - 1 ascending of w[t][j][k] * feat[r][t Cf + k]) + b[t][j] -- the operations of
+ *           t2h_routed_head_argmax in their order: both kernels see the same float for every class;
+ *   l_j   = raw_j / temp;
+ *   theta = the row threshold of truncated sampling on l (t2h_truncation_threshold; -inf with both rules off);
+ *   tok   = argmax over {j : l_j >= theta} of expf(l_j - max l) / E[r][j], first index wins (the race of
+ *           t2h_confidence_tail);  out_lists[t][r] = tok, out_lists[h != t][r] = -1.
+ * A row whose tex lies outside [0, n_heads) gets -1 in every list (logp -inf, logits_ws untouched).
+ * Rules: temp / top_k / top_p_q of the struct (params == NULL; temp > 0), or row r's = params[r / rows_per_sample]
+ *   (rows_per_sample divides n; the table's values are the caller's to validate, as for t2h_sample_heads_per_sample).
+ *   Top-p needs n_class <= 2048 (with a table: the whole launch).
+ * Noise: expo [n][n_class] explicit (row r reads expo[r]), or expo == NULL: E[r][j] = element
+ *   ((noise_row0 + r) * n_class + j) of the tensor torch's `torch.empty(rows, n_class).exponential_()` draws at generator
+ *   (philox_seed, philox_offset), philox_grid_threads = 256 * the grid ATen launches for that WHOLE tensor
+ *   (t2h_philox_exponential_f32): a caller that decodes a batch in chunks gives every chunk its rows of one draw.
+ * Optional outputs (NULL: skipped): logp [n] = l_tok - max l - log(sum_j expf(l_j - max l)), the log-probability of
+ *   the drawn code under the FULL softmax at that temperature (truncation changes tok only); logits_ws [n][n_class] =
+ *   the l the race saw. */
+typedef struct t2h_routed_sample_args {
+  const float* feat;        /* [n][ldf] */
+  int32_t ldf;
+  const float* w;           /* [n_heads][n_class][Cf] */
+  const float* b;           /* [n_heads][n_class] */
+  const int64_t* tex;       /* [n] */
+  int64_t* out_lists;       /* [n_heads][n] */
+  int32_t n, n_heads, Cf, n_class;
+  float temp;
+  int32_t top_k;
+  uint32_t top_p_q;
+  const float* expo;
+  uint64_t philox_seed, philox_offset;
+  uint32_t philox_grid_threads;
+  int64_t noise_row0;
+  float* logp;
+  float* logits_ws;
+} t2h_routed_sample_args;
+int t2h_routed_head_sample(const t2h_routed_sample_args* args, const t2h_sample_params* params,
+                           int32_t rows_per_sample, void* stream);
+
 /* ------------------------------------------------------ layout / misc ------ */
 /* F.one_hot(segm).permute(0,3,1,2) (models/sample_model.py:332-335) as NHWC
  * with the channel dim zero-padded to Cpad */

@@ -93,6 +93,17 @@ class SampleParams(ctypes.Structure):
     _fields_ = [('temp', c_f32), ('top_k', c_i32), ('top_p_q', ctypes.c_uint32)]
 
 
+class RoutedSampleArgs(ctypes.Structure):
+    """struct t2h_routed_sample_args (include/t2h_hip.h)."""
+    _fields_ = [
+        ('feat', c_vp), ('ldf', c_i32), ('w', c_vp), ('b', c_vp), ('tex', c_vp), ('out_lists', c_vp),
+        ('n', c_i32), ('n_heads', c_i32), ('Cf', c_i32), ('n_class', c_i32),
+        ('temp', c_f32), ('top_k', c_i32), ('top_p_q', ctypes.c_uint32),
+        ('expo', c_vp), ('philox_seed', ctypes.c_uint64), ('philox_offset', ctypes.c_uint64),
+        ('philox_grid_threads', ctypes.c_uint32), ('noise_row0', c_i64), ('logp', c_vp), ('logits_ws', c_vp),
+    ]
+
+
 # name -> (restype, argtypes); must list EVERY symbol declared in include/t2h_hip.h
 SIGNATURES = {
     't2h_gemm_split_f32': (ctypes.c_int, [ctypes.POINTER(GemmSplitArgs), c_vp]),
@@ -165,6 +176,7 @@ SIGNATURES = {
                                                     c_i32, c_i32, c_vp]),
     't2h_routed_head_argmax': (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32,
                                               c_i32, c_vp]),
+    't2h_routed_head_sample': (ctypes.c_int, [ctypes.POINTER(RoutedSampleArgs), c_vp, c_i32, c_vp]),
     't2h_onehot_nhwc_f32': (ctypes.c_int, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp]),
     't2h_nchw_to_nhwc_f32': (ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
     't2h_nhwc_to_nchw_f32': (ctypes.c_int, [c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp]),

@@ -1098,6 +1098,114 @@ __global__ __launch_bounds__(NT == 64 ? 64 * CP_ROWS : SH_THREADS) void trunc_th
     kept[row] = n_kept;
   }
 }
+
+// ---- sampled bottom-index refinement: routed_head_argmax_kernel of vq.hip with a draw in place of the
+// maximum.  One workgroup per token, the token's Cf features in LDS, thread t owns classes t, t + 256, ...: the logit of
+// a class is that kernel's serial fma chain + bias (the same float), divided by the temperature into LDS; then the row
+// maximum, the threshold of truncated sampling (the workgroup form of trunc_select) and conf_pick_kernel's race, noise
+// explicit or element (noise_row0 + row, j) of torch's whole-tensor exponential_ draw.
+constexpr int RS_THREADS = 256;
+template <bool TRUNC, bool PER_SAMPLE>
+__global__ __launch_bounds__(RS_THREADS) void routed_head_sample_kernel(const t2h_routed_sample_args a,
+                                                                        const t2h_sample_params* __restrict__ params,
+                                                                        int T) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];  // Cf features, n_class logits, 3 * NW reduce slots
+  constexpr int NW = RS_THREADS / 64;
+  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  float* fs = lds;
+  float* lg = lds + a.Cf;
+  float* red = lg + a.n_class;
+  const int64_t tex = a.tex[row];
+  for (int hd = tid; hd < a.n_heads; hd += RS_THREADS)
+    if (hd != tex) a.out_lists[(int64_t)hd * a.n + row] = -1;
+  if (tex < 0 || tex >= a.n_heads) {  // (uniform over the workgroup)
+    if (tid == 0 && a.logp) a.logp[row] = -INFINITY;
+    return;
+  }
+  const int t = (int)tex;
+  float temp = a.temp;
+  int top_k = a.top_k;
+  uint32_t top_p_q = a.top_p_q;
+  if constexpr (PER_SAMPLE) {
+    const sample_settings st = sample_settings_of(params, row, T, a.n_class);
+    temp = st.temp;
+    top_k = st.top_k;
+    top_p_q = st.top_p_q;
+  }
+  for (int k = tid; k < a.Cf; k += RS_THREADS) fs[k] = a.feat[(int64_t)row * a.ldf + t * a.Cf + k];
+  __syncthreads();
+  float mx = -INFINITY;
+  for (int j = tid; j < a.n_class; j += RS_THREADS) {
+    const float* wr = a.w + ((int64_t)t * a.n_class + j) * a.Cf;
+    float acc = 0.f;
+    for (int k = 0; k < a.Cf; ++k) acc = fmaf(wr[k], fs[k], acc);
+    acc += a.b[t * a.n_class + j];
+    const float l = acc / temp;
+    lg[j] = l;
+    if (a.logits_ws) a.logits_ws[(int64_t)row * a.n_class + j] = l;
+    mx = fmaxf(mx, l);
+  }
+  mx = wave_max(mx);
+  if (lane == 0) red[wave] = mx;
+  __syncthreads();  // (also: every logit of the row is in LDS)
+  mx = red[0];
+#pragma unroll
+  for (int k = 1; k < NW; ++k) mx = fmaxf(mx, red[k]);
+  float theta = -INFINITY;
+  if constexpr (TRUNC) {  // only the token changes: se / logp below stay those of the full softmax
+    __shared__ trunc_lds tr;
+    int kept;
+    if (!PER_SAMPLE || top_k != 0 || top_p_q != 0)  // (uniform over the workgroup)
+      theta = trunc_unkey(trunc_select<RS_THREADS>(lg, a.n_class, mx, top_k, top_p_q, &tr, tid, &kept));
+  }
+  const float* er = a.expo ? a.expo + (int64_t)row * a.n_class : nullptr;
+  const uint64_t e0 = (uint64_t)(a.noise_row0 + row) * (uint64_t)a.n_class;
+  float best = -1.f, se = 0.f;
+  int best_j = 0x7fffffff;
+  for (int j = tid; j < a.n_class; j += RS_THREADS) {
+    const float q = er ? er[j] : torch_exponential_at(a.philox_seed, a.philox_offset, a.philox_grid_threads, e0 + j);
+    const float ex = expf(lg[j] - mx);
+    const float sc = ex / q;
+    se += ex;
+    if (TRUNC && !(lg[j] >= theta)) continue;
+    if (sc > best) {
+      best = sc;
+      best_j = j;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ob = __shfl_xor(best, o, 64);
+    const int oj = __shfl_xor(best_j, o, 64);
+    if (ob > best || (ob == best && oj < best_j)) {
+      best = ob;
+      best_j = oj;
+    }
+  }
+  se = wave_sum(se);
+  float* reds = red + NW;
+  int* redj = reinterpret_cast<int*>(red + 2 * NW);
+  __syncthreads();  // (red[] has been read by every thread)
+  if (lane == 0) {
+    red[wave] = best;
+    reds[wave] = se;
+    redj[wave] = best_j;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    se = reds[0];
+    for (int k = 1; k < NW; ++k) {
+      se += reds[k];
+      if (red[k] > best || (red[k] == best && redj[k] < best_j)) {
+        best = red[k];
+        best_j = redj[k];
+      }
+    }
+    if (best_j >= a.n_class) best_j = 0;  // all-NaN scores: see sample_row
+    a.out_lists[(int64_t)t * a.n + row] = best_j;
+    if (a.logp) a.logp[row] = (lg[best_j] - mx) - logf(se);
+  }
+}
 }  // namespace
 
 // top_k >= n_class and top_p_q == 2^20 cut nothing: off (the existing kernels)
@@ -1149,6 +1257,41 @@ extern "C" int t2h_truncation_threshold_per_row(const float* logits, int32_t n_r
   T2H_REQUIRE(n_rows > 0 && n_class > 0 && (scope == 0 || scope == 1), "t2h_truncation_threshold_per_row: bad arguments");
   T2H_PER_SAMPLE_REQUIRE("t2h_truncation_threshold_per_row", params, rows_per_sample, n_rows, n_class);
   return trunc_threshold_launch<true>(logits, n_rows, n_class, 0, 0, params, rows_per_sample, scope, theta, kept, stream);
+}
+
+// params == NULL: the struct's scalars (the instance without truncation code where they cut nothing); else the
+// PER_SAMPLE instance (a.temp / a.top_k / a.top_p_q are not read).  Nothing is launched on an error.
+extern "C" int t2h_routed_head_sample(const t2h_routed_sample_args* args, const t2h_sample_params* params,
+                                      int32_t rows_per_sample, void* stream) {
+  T2H_REQUIRE(args != nullptr, "t2h_routed_head_sample: args is NULL");
+  t2h_routed_sample_args a = *args;
+  if (params) a.temp = 1.f, a.top_k = 0, a.top_p_q = 0;
+  T2H_REQUIRE(a.feat && a.w && a.b && a.tex && a.out_lists, "t2h_routed_head_sample: NULL pointer");
+  T2H_REQUIRE(a.n > 0 && a.n_heads > 0 && a.Cf > 0 && a.n_class > 0 && (int64_t)a.ldf >= (int64_t)a.n_heads * a.Cf,
+              "t2h_routed_head_sample: bad shape (n=%d n_heads=%d Cf=%d n_class=%d ldf=%d)", a.n, a.n_heads, a.Cf,
+              a.n_class, a.ldf);
+  T2H_REQUIRE(a.temp > 0.f, "t2h_routed_head_sample: temp must be > 0");
+  T2H_REQUIRE(a.expo != nullptr || (a.philox_grid_threads != 0 && a.philox_offset % 4 == 0 && a.noise_row0 >= 0),
+              "t2h_routed_head_sample: no noise (expo, or philox_grid_threads, an offset that is a multiple of 4 and "
+              "noise_row0 >= 0)");
+  T2H_TRUNC_REQUIRE("t2h_routed_head_sample", a.top_k, a.top_p_q, a.n_class);
+  if (params) T2H_PER_SAMPLE_REQUIRE("t2h_routed_head_sample", params, rows_per_sample, a.n, a.n_class);
+  const size_t lds = ((size_t)a.Cf + a.n_class + 3 * (RS_THREADS / 64)) * sizeof(float);
+  if (lds > 48 * 1024) {
+    t2h_set_error("t2h_routed_head_sample: Cf=%d + n_class=%d floats do not fit the kernel's LDS", a.Cf, a.n_class);
+    return T2H_ERR_UNSUPPORTED;
+  }
+  const bool trunc = trunc_settings(a.n_class, &a.top_k, &a.top_p_q);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (params)
+    hipLaunchKernelGGL((routed_head_sample_kernel<true, true>), dim3(a.n), dim3(RS_THREADS), lds, s, a, params,
+                       rows_per_sample);
+  else if (trunc)
+    hipLaunchKernelGGL((routed_head_sample_kernel<true, false>), dim3(a.n), dim3(RS_THREADS), lds, s, a, params, 0);
+  else
+    hipLaunchKernelGGL((routed_head_sample_kernel<false, false>), dim3(a.n), dim3(RS_THREADS), lds, s, a, params, 0);
+  T2H_CHECK_LAUNCH("t2h_routed_head_sample");
+  return T2H_OK;
 }
 
 extern "C" int64_t t2h_confidence_group_ws_ints(int32_t n, int32_t n_heads) {

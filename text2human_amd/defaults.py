@@ -147,6 +147,19 @@ def with_truncation(opt, top_k=None, top_p=None):
     return opt
 
 
+def with_refine_sampling(opt, temp=None, top_k=None, top_p=None):
+    """`opt` with the keys that make sample_and_refine / inference DRAW the bottom (detail) indices from the
+    index-prediction heads' softmax instead of taking its mode (options.refine_sampling; all None: off).  Returns opt."""
+    from . import options
+    options.refine_values(temp, top_k, top_p)
+    for key, v in zip(options.REFINE_KEYS, (temp, top_k, top_p)):
+        if v is None:
+            opt.pop(key, None)
+        else:
+            opt[key] = v
+    return opt
+
+
 def write_yaml(opt, path):
     with open(path, 'w') as f:
         yaml.safe_dump(dict(opt), f, sort_keys=False)

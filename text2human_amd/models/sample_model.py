@@ -8,6 +8,7 @@ the attributes callers read: .segm, .segm_tokens, .texture_mask, .device,
 every tensor op runs in hand-written HIP kernels (libt2h_hip.so) through
 text2human_amd.engine, batched over images, with no PyTorch compute fallback.
 """
+import collections
 import logging
 import os
 
@@ -22,6 +23,11 @@ logger = logging.getLogger('base')
 # images decoded per pass: the decode's activations take ~0.6 GB / image at 512x256 (2.4 GB at 1024x512, where a pass
 # takes a quarter of this); T2H_DECODE_CHUNK overrides (a box with less free HBM, or larger passes on an idle 288 GB)
 DECODE_CHUNK = max(1, int(os.environ.get('T2H_DECODE_CHUNK', '8')))
+
+# One refine-sampled decode: values = (temp, top_k, top_p) as validated scalars, or table = the
+# per-image t2h_sample_params on the device; the noise of all `rows` = B * 512 token rows is ONE [rows, n_class]
+# exponential_ draw of the generator -- philox = its (seed, offset), computed in the kernel, or expo = the tensor.
+RefineDraw = collections.namedtuple('RefineDraw', 'values table philox expo rows')
 
 
 class BaseSampleModel():
@@ -240,12 +246,17 @@ class BaseSampleModel():
 
     @torch.no_grad()
     def edit_and_refine(self, top_indices_list, region=None, labels=None, bot_indices_list=None, save_dir=None,
-                        img_name=None, order='random', rounds=None, choice_temp=4.5, top_k=None, top_p=None, temp=1.0):
+                        img_name=None, order='random', rounds=None, choice_temp=4.5, top_k=None, top_p=None, temp=1.0,
+                        refine_temp=None, refine_top_k=None, refine_top_p=None):
         """Region edit end to end: resample the top tokens of the region (region_keep), predict the bottom indices,
         keep `bot_indices_list` (e.g. a photo's bot_encode) outside the region if given, decode.  Return values and
         files follow sample_and_refine: with save_dir and img_name both None the first image f32 [1, 3, H, W];
         otherwise {save_dir}/{img_name[i]} PNGs are written and their uint8 [B, H, W, 3] pixels returned.  The edited
-        index lists are left in self.edit_top_indices_list / self.edit_bot_indices_list (18 x int64 [B, 512])."""
+        index lists are left in self.edit_top_indices_list / self.edit_bot_indices_list (18 x int64 [B, 512]).
+        refine_temp / refine_top_k / refine_top_p: the bottom indices are drawn (decode_indices); kept tokens keep
+        theirs whatever these are."""
+        refine_kw = dict(refine_temp=refine_temp, refine_top_k=refine_top_k, refine_top_p=refine_top_p)
+        options.refine_values(refine_temp, refine_top_k, refine_top_p, batch=self.batch_size)  # (before anything is drawn)
         keep = self.region_keep(region, labels)
         keep_rows = keep.reshape(-1).contiguous()
         bot = None
@@ -264,12 +275,13 @@ class BaseSampleModel():
             self.batch_size, self.texture_mask = 1, self.texture_mask[:1]
             try:
                 one = (bot[:, :t_len].contiguous(), keep_rows[:t_len]) if bot is not None else None
-                img, _, inter = self.decode_indices([t[:1] for t in top], return_inter=True, bot_keep=one)
+                img, _, inter = self.decode_indices([t[:1] for t in top], return_inter=True, bot_keep=one,
+                                                    **self._refine_first_image(refine_kw))
             finally:
                 self.batch_size, self.texture_mask = keep_b, keep_mask
             self._edit_results(top, inter, 1)
             return img
-        _, u8, inter = self.decode_indices(top, want_u8=True, return_inter=True, bot_keep=bot_keep)
+        _, u8, inter = self.decode_indices(top, want_u8=True, return_inter=True, bot_keep=bot_keep, **refine_kw)
         self._edit_results(top, inter, self.batch_size)
         save_u8_images(u8, save_dir, img_name)
         return u8
@@ -292,35 +304,87 @@ class BaseSampleModel():
         zq = ops.codebook_gather_tex(top_lists, tex_tok.reshape(-1), P['top.books'])
         return ops.gemm(zq, P['top.pq.w'], bias=P['top.pq.b'])
 
-    def _bot_indices(self, top_quant_rows, tex_tok, b):
-        """R-3 batched: UNet -> all 18 head convs as one GEMM -> routed 1x1 + argmax."""
+    def _head_features(self, top_quant_rows, b):
+        """R-3: UNet -> all 18 head convs as one GEMM -> rows [b*512, 18 * cf]."""
         P = self.P
         h, w = self.shape
         feat, _, _ = self.index_pred_guidance_encoder.forward(top_quant_rows, b, h, w)
-        hc = ops.conv3x3(feat, P['ipd.conv.w'], b, h, w, feat.shape[1], bias=P['ipd.conv.b'],
-                         act=ACT_RELU)
-        return ops.routed_head_argmax(hc, P['ipd.seg.w'], P['ipd.seg.b'], tex_tok.reshape(-1),
-                                      self.ipd['n_heads'], self.ipd['cf'], self.ipd['n_class'])
+        return ops.conv3x3(feat, P['ipd.conv.w'], b, h, w, feat.shape[1], bias=P['ipd.conv.b'], act=ACT_RELU)
+
+    def _bot_indices(self, top_quant_rows, tex_tok, b, refine=None, row0=0):
+        """R-3 batched: UNet -> all 18 head convs as one GEMM -> routed 1x1 + argmax.  refine (RefineDraw; None: the
+        reference's argmax): the index of every token is drawn instead (t2h_routed_head_sample), these b images being
+        token rows row0 .. row0 + b*512 - 1 of the draw's batch."""
+        P = self.P
+        hc = self._head_features(top_quant_rows, b)
+        if refine is None:
+            return ops.routed_head_argmax(hc, P['ipd.seg.w'], P['ipd.seg.b'], tex_tok.reshape(-1),
+                                          self.ipd['n_heads'], self.ipd['cf'], self.ipd['n_class'])
+        t_len = self.shape[0] * self.shape[1]
+        if refine.table is not None:
+            rules = dict(params=refine.table[row0 // t_len:row0 // t_len + b], rows_per_sample=t_len)
+        else:
+            rules = dict(zip(('temp', 'top_k', 'top_p'), refine.values))
+        if refine.philox is not None:
+            noise = dict(philox=refine.philox, noise_rows=refine.rows, noise_row0=row0)
+        else:
+            noise = dict(expo=refine.expo[row0:row0 + b * t_len])
+        return ops.routed_head_sample(hc, P['ipd.seg.w'], P['ipd.seg.b'], tex_tok.reshape(-1).contiguous(),
+                                      self.ipd['n_heads'], self.ipd['cf'], self.ipd['n_class'], **rules, **noise)
+
+    def _refine_options(self):
+        """refine_temp / refine_top_k / refine_top_p of the options as keyword arguments ({}: absent, the argmax)."""
+        vals = options.refine_sampling(self.opt)
+        return dict(zip(options.REFINE_KEYS, vals)) if vals is not None else {}
+
+    @staticmethod
+    def _refine_first_image(kw):
+        """the refine arguments of a batch, for a decode of its first image alone"""
+        return {k: ([options.per_image_values(len(v), v, k)[0]] if options.is_per_image(v) else v) for k, v in kw.items()}
+
+    def _refine_draw(self, batch, refine_temp, refine_top_k, refine_top_p):
+        """-> None (nothing set: the argmax, the generator is not touched) or the RefineDraw of a decode of `batch`
+        images.  The arguments are validated first (ValueError); then the generator is read ONCE and advanced by one
+        [batch * 512, n_class] exponential_ draw -- every chunk, and a re-run after an overflow, uses this draw."""
+        vals = options.refine_values(refine_temp, refine_top_k, refine_top_p, batch=batch)
+        if vals is None:
+            return None
+        n_class = self.ipd['n_class']
+        sp = ops.sampling_params(batch, *vals, n_class=n_class)
+        table = ops.sample_params_tensor(sp.table, self.device) if sp.table is not None else None
+        n = batch * self.shape[0] * self.shape[1]
+        src = self.noise if self.noise is not None else engine.TorchDeviceNoise(self.device)
+        philox = expo = None
+        if isinstance(src, engine.TorchDeviceNoise) and src.emulation_ok(n, n_class):
+            gen, _ = src.generator()
+            philox = (gen.initial_seed(), gen.get_offset())
+            gen.set_offset(philox[1] + ops.torch_draw_geometry(n * n_class, self.device)[1])
+        else:  # (another noise source, or a torch build whose Philox draws the kernels do not reproduce)
+            expo = src.exponential(0, 0, (n, n_class)).to(self.device, torch.float32).contiguous()
+        return RefineDraw(vals, table, philox, expo, n)
 
     @torch.no_grad()
-    def bot_index_prediction(self, feature_top, texture_mask):
+    def bot_index_prediction(self, feature_top, texture_mask, refine_temp=None, refine_top_k=None, refine_top_p=None):
         """models/sample_model.py:183-213.  feature_top f32 [B,256,32,16] (NCHW,
-        as the reference passes it) -> list of 18 int64 [B,32,16]."""
+        as the reference passes it) -> list of 18 int64 [B,32,16].  refine_temp / refine_top_k / refine_top_p: see
+        decode_indices."""
         b = feature_top.shape[0]
+        refine = self._refine_draw(b, refine_temp, refine_top_k, refine_top_p)
         tex_tok = self._texture_tokens(texture_mask.to(self.device))
         rows = ops.nchw_to_nhwc(feature_top.to(self.device, torch.float32))
-        lists = self._bot_indices(rows, tex_tok, b)
+        lists = self._bot_indices(rows, tex_tok, b, refine=refine)
         return [lists[i].view(b, self.shape[0], self.shape[1]) for i in range(lists.shape[0])]
 
     # ------------------------------------------------------------ stage D
-    def _decode(self, top_lists, tex_tok, b, want_u8=False, return_inter=False, upscale=False, bot_keep=None):
+    def _decode(self, top_lists, tex_tok, b, want_u8=False, return_inter=False, upscale=False, bot_keep=None,
+                refine=None, row0=0):
         """sample_and_refine body after sample_fn (models/sample_model.py:220-246),
         batched.  top_lists int64 [18, b*512].  bot_keep = (bot_lists [18, b*512], keep uint8 [b*512]): the
-        predicted bottom indices are replaced by those where keep (region editing)."""
+        predicted bottom indices are replaced by those where keep (region editing).  refine / row0: see _bot_indices."""
         P = self.P
         h, w = self.shape
         top_quant = self._top_quant_rows(top_lists, tex_tok)
-        bot_lists = self._bot_indices(top_quant, tex_tok, b)
+        bot_lists = self._bot_indices(top_quant, tex_tok, b, refine=refine, row0=row0)
         if bot_keep is not None:
             ops.merge_kept_indices(bot_keep[0], bot_keep[1], bot_lists)
         quant_bot = ops.codebook_gather_fold(bot_lists, tex_tok.reshape(-1), P['bot.books'], b, h, w)
@@ -333,26 +397,34 @@ class BaseSampleModel():
         return img, u8
 
     @torch.no_grad()
-    def decode_indices(self, top_indices_list, want_u8=False, return_inter=False, upscale=False, bot_keep=None):
+    def decode_indices(self, top_indices_list, want_u8=False, return_inter=False, upscale=False, bot_keep=None,
+                       refine_temp=None, refine_top_k=None, refine_top_p=None):
         """Batched refine + decode of sampled top indices (list of 18 [B,512]).
         upscale=True: 1024x512 output -- both quantised latents are nearest-x2
         upsampled before the (fully convolutional) decoders, the interpretation
         of BASELINE.json configs[4] given in SURVEY.md 8(d).  bot_keep (region editing, edit_and_refine): see
-        _decode."""
+        _decode.  refine_temp / refine_top_k / refine_top_p (not in the reference): any of them set
+        DRAWS the bottom (detail) index of every token from the index-prediction head's softmax at refine_temp (default
+        1), among the refine_top_k most likely codes / the most likely codes holding refine_top_p of the probability,
+        instead of taking its mode; each a scalar or a sequence with one entry per image.  Such a call consumes torch's
+        GPU generator as ONE [B*512, n_class] exponential_ draw; with all three None the generator is not touched."""
+        # the draw is fixed BEFORE the first attempt: the re-run below uses the same (seed, offset), and the generator
+        # is advanced once
+        refine = self._refine_draw(self.batch_size, refine_temp, refine_top_k, refine_top_p)
         try:
-            return self._decode_indices(top_indices_list, want_u8, return_inter, upscale, bot_keep)
+            return self._decode_indices(top_indices_list, want_u8, return_inter, upscale, bot_keep, refine)
         except engine.SplitOverflowError as e:
-            # (decode draws no random numbers: simply once more, convolutions on the exact-fp32 kernels)
+            # (once more, convolutions on the exact-fp32 kernels)
             if not _overflow_fallback('VQGAN refine / decode', 'T2H_SPLIT_CONV', e):
                 raise
             keep = self.decoder.use_split, self.bot_decoder_res.use_split
             self.decoder.use_split = self.bot_decoder_res.use_split = False
             try:
-                return self._decode_indices(top_indices_list, want_u8, return_inter, upscale, bot_keep)
+                return self._decode_indices(top_indices_list, want_u8, return_inter, upscale, bot_keep, refine)
             finally:
                 self.decoder.use_split, self.bot_decoder_res.use_split = keep
 
-    def _decode_indices(self, top_indices_list, want_u8, return_inter, upscale, bot_keep=None):
+    def _decode_indices(self, top_indices_list, want_u8, return_inter, upscale, bot_keep=None, refine=None):
         b = self.batch_size
         tex_tok = self._texture_tokens(self.texture_mask)
         top = torch.stack([t.reshape(-1) for t in top_indices_list]).contiguous()
@@ -364,7 +436,8 @@ class BaseSampleModel():
             bk = ((bot_keep[0][:, s * t_len:e * t_len].contiguous(), bot_keep[1][s * t_len:e * t_len])
                   if bot_keep is not None else None)
             res = self._decode(top[:, s * t_len:e * t_len].contiguous(), tex_tok[s:e], e - s,
-                               want_u8=want_u8, return_inter=return_inter, upscale=upscale, bot_keep=bk)
+                               want_u8=want_u8, return_inter=return_inter, upscale=upscale, bot_keep=bk,
+                               refine=refine, row0=s * t_len)
             imgs.append(res[0])
             u8s.append(res[1])
             if return_inter:
@@ -385,6 +458,7 @@ class BaseSampleModel():
         confidence = self._confidence_options()
         top_k, top_p = self._truncation_options()  # (options: sample_top_k / sample_top_p)
         trunc = {k: v for k, v in (('top_k', top_k), ('top_p', top_p)) if v is not None}
+        refine_kw = self._refine_options()  # (options: refine_temp / refine_top_k / refine_top_p)
         if confidence is not None:  # (options: sample_order: confidence)
             sampled_top_indices_list = self.sample_fn_confidence(rounds=confidence[0], temp=1, choice_temp=confidence[1],
                                                                  **trunc)
@@ -397,11 +471,12 @@ class BaseSampleModel():
             keep_b, keep_mask = self.batch_size, self.texture_mask
             self.batch_size, self.texture_mask = 1, self.texture_mask[:1]
             try:
-                img, _ = self.decode_indices([t[:1] for t in sampled_top_indices_list])
+                img, _ = self.decode_indices([t[:1] for t in sampled_top_indices_list],
+                                             **self._refine_first_image(refine_kw))
             finally:
                 self.batch_size, self.texture_mask = keep_b, keep_mask
             return img
-        _, u8 = self.decode_indices(sampled_top_indices_list, want_u8=True)
+        _, u8 = self.decode_indices(sampled_top_indices_list, want_u8=True, **refine_kw)
         save_u8_images(u8, save_dir, img_name)
 
     def inference(self, data_loader, save_dir):

@@ -1211,6 +1211,53 @@ def routed_head_argmax(feat, w, b, tex, n_heads, cf, n_class):
     return out
 
 
+def routed_head_sample(feat, w, b, tex, n_heads, cf, n_class, temp=1.0, top_k=None, top_p=None, params=None,
+                       rows_per_sample=None, expo=None, philox=None, noise_rows=None, noise_row0=0, want_logp=False,
+                       want_logits=False):
+    """routed_head_argmax with a draw in place of the maximum (t2h_routed_head_sample): the detail code
+    of row r is drawn from softmax(head(feat[r]) / temp), truncated by top_k / top_p (truncation_settings; None = off).
+    params (sample_params_tensor) + rows_per_sample: row r uses params[r // rows_per_sample]; temp / top_k / top_p are
+    then not read.  Noise: expo f32 [n, n_class], or philox = (seed, offset) of torch's generator before a
+    `torch.empty(noise_rows, n_class).exponential_()` draw (noise_rows defaults to n), of which this launch takes rows
+    noise_row0 .. noise_row0 + n - 1.  -> out_lists [n_heads, n] i64 (-1 off-texture); with want_logp / want_logits
+    the tuple (out_lists, logp f32 [n] or None, logits f32 [n, n_class] or None)."""
+    _chk_f32(feat, w, b)
+    _chk_i64(tex)
+    n = feat.shape[0]
+    assert w.is_contiguous() and b.is_contiguous() and tex.is_contiguous() and tex.numel() == n
+    assert tuple(w.shape) == (n_heads, n_class, cf) and b.numel() == n_heads * n_class
+    if (expo is None) == (philox is None):
+        raise ValueError('routed_head_sample: give exactly one of expo (an explicit draw) or philox (seed, offset)')
+    a = _lib.RoutedSampleArgs()
+    if params is None:
+        if isinstance(temp, bool) or not isinstance(temp, numbers.Real) or not float(temp) > 0.0 or float(temp) == float('inf'):
+            raise ValueError(f'temp must be a finite number > 0, got {temp!r}')
+        a.temp = float(temp)
+        a.top_k, a.top_p_q = truncation_settings(top_k, top_p, n_class)
+    out = torch.empty((n_heads, n), device=feat.device, dtype=torch.int64)
+    logp = torch.empty(n, device=feat.device, dtype=torch.float32) if want_logp else None
+    logits = torch.empty((n, n_class), device=feat.device, dtype=torch.float32) if want_logits else None
+    a.feat, a.ldf, a.w, a.b, a.tex, a.out_lists = feat.data_ptr(), _rows(feat), w.data_ptr(), b.data_ptr(), tex.data_ptr(), out.data_ptr()
+    a.n, a.n_heads, a.Cf, a.n_class = n, int(n_heads), int(cf), int(n_class)
+    if expo is not None:
+        _chk_f32(expo)
+        assert expo.is_contiguous() and tuple(expo.shape) == (n, n_class)
+        a.expo = expo.data_ptr()
+    else:
+        total = n if noise_rows is None else int(noise_rows)
+        assert 0 <= int(noise_row0) and int(noise_row0) + n <= total
+        a.philox_seed, a.philox_offset = int(philox[0]) & 0xFFFFFFFFFFFFFFFF, int(philox[1])
+        a.philox_grid_threads = torch_draw_geometry(total * n_class, feat.device)[0]
+        a.noise_row0 = int(noise_row0)
+    a.logp = logp.data_ptr() if logp is not None else None
+    a.logits_ws = logits.data_ptr() if logits is not None else None
+    T = 0
+    if params is not None:
+        T = _chk_params(params, rows_per_sample, n)
+    check(_lib.load().t2h_routed_head_sample(ctypes.byref(a), _p(params), T, _stream()), 't2h_routed_head_sample')
+    return (out, logp, logits) if (want_logp or want_logits) else out
+
+
 def onehot_nhwc(segm, n_cls, cpad):
     _chk_f32(segm)
     n_pix = segm.numel()

@@ -156,6 +156,49 @@ def sampling_truncation(opt):
     return top_k, top_p
 
 
+# Sampled bottom-index refinement.  Absent keys = off = the argmax of the index-prediction heads.
+REFINE_KEYS = ('refine_temp', 'refine_top_k', 'refine_top_p')
+
+
+def refine_values(temp=None, top_k=None, top_p=None, batch=None):
+    """The public refine_temp / refine_top_k / refine_top_p, validated: each a scalar or a per-image sequence
+    (per_image_values; its length is checked against `batch` if given).  -> None if all three are None (sampling off),
+    else (temp, top_k, top_p) with temp defaulting to 1.0.  ValueError names the option (and the image)."""
+    import numbers
+    if temp is None and top_k is None and top_p is None:
+        return None
+    temp = 1.0 if temp is None else temp
+    for name, value in zip(REFINE_KEYS, (temp, top_k, top_p)):
+        if batch is not None:
+            vals = per_image_values(batch, value, name)
+        else:
+            vals = per_image_values(len(value) if isinstance(value, (list, tuple)) else value.shape[0], value,
+                                    name) if is_per_image(value) else None
+        for i, v in enumerate([value] if vals is None else vals):
+            who = name if vals is None else f'{name}, image {i}'
+            try:
+                if name == 'refine_temp':
+                    if isinstance(v, bool) or not isinstance(v, numbers.Real) or not float(v) > 0.0 or float(v) == float('inf'):
+                        raise ValueError(f'must be a finite number > 0, got {v!r}')
+                elif name == 'refine_top_k':
+                    truncation_settings(v, None)
+                else:
+                    truncation_settings(None, v)
+            except ValueError as e:
+                raise ValueError(f'{who}: {e}') from None
+    return temp, top_k, top_p
+
+
+def refine_sampling(opt):
+    """-> refine_values of the options `refine_temp` / `refine_top_k` / `refine_top_p` (None: absent, sampling off).
+    The options are scalars, like `sample_top_k` / `sample_top_p`: a dataset run has no per-image identity."""
+    vals = [opt.get(k) for k in REFINE_KEYS]
+    for k, v in zip(REFINE_KEYS, vals):
+        if is_per_image(v):
+            raise ValueError(f'{k}: the option is one value for the whole run, got {v!r}')
+    return refine_values(*vals)
+
+
 def dict2str(opt, indent_level=1):
     msg = ''
     pad = ' ' * (indent_level * 2)

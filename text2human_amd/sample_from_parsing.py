@@ -105,6 +105,14 @@ def cli_parser():
     ap.add_argument('--top-p', type=float, default=None,
                     help='index sampler: draw every token from the most likely classes that hold this share of the '
                          'probability (overrides sample_top_p)')
+    ap.add_argument('--refine-temp', type=float, default=None,
+                    help='refinement: draw the bottom (detail) indices from the index-prediction softmax at this '
+                         'temperature instead of taking its mode (overrides refine_temp)')
+    ap.add_argument('--refine-top-k', type=int, default=None,
+                    help='refinement: draw every detail code among its k most likely classes (overrides refine_top_k)')
+    ap.add_argument('--refine-top-p', type=float, default=None,
+                    help='refinement: draw every detail code from the most likely classes that hold this share of the '
+                         'probability (overrides refine_top_p)')
     return ap
 
 
@@ -112,11 +120,13 @@ def apply_cli(opt, args):
     """The command line's overrides of the YAML's sampling keys, validated (a bad value ends the run here, before the
     checkpoints are read).  Returns opt."""
     for key, v in (('sample_order', args.order), ('confidence_rounds', args.rounds), ('sample_top_k', args.top_k),
-                   ('sample_top_p', args.top_p)):
+                   ('sample_top_p', args.top_p), ('refine_temp', args.refine_temp),
+                   ('refine_top_k', args.refine_top_k), ('refine_top_p', args.refine_top_p)):
         if v is not None:
             opt[key] = v
     options.sampling_order(opt)
     options.sampling_truncation(opt)
+    options.refine_sampling(opt)
     return opt
 
 
