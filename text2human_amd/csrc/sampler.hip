@@ -190,38 +190,41 @@ struct sample_settings {
   int top_k;
   uint32_t top_p_q;
 };
-__device__ __forceinline__ sample_settings sample_settings_of(const t2h_sample_params* __restrict__ params, int row, int T,
-                                                             int n_class) {
-  const t2h_sample_params p = params[row / T];  // (row is uniform over the wave: one scalar load)
-  sample_settings s;
-  s.temp = p.temp;
-  s.top_k = (p.top_k <= 0 || p.top_k >= n_class) ? 0 : p.top_k;
-  s.top_p_q = p.top_p_q >= (1u << 20) ? 0u : p.top_p_q;
+template <bool PER_SAMPLE>
+__device__ __forceinline__ sample_settings row_settings(float temp, int top_k, uint32_t top_p_q,
+                                                       const t2h_sample_params* __restrict__ params, int row, int T,
+                                                       int n_class) {
+  sample_settings s = {temp, top_k, top_p_q};
+  if constexpr (PER_SAMPLE) {
+    const t2h_sample_params p = params[row / T];  // (row is uniform over the wave: one scalar load)
+    s.temp = p.temp;
+    s.top_k = (p.top_k <= 0 || p.top_k >= n_class) ? 0 : p.top_k;
+    s.top_p_q = p.top_p_q >= (1u << 20) ? 0u : p.top_p_q;
+  }
   return s;
 }
 
-// One workgroup per token row; rows that are not (changed && of this head's
-// texture) exit at once.  LN_f -> 512->n_class head (wave-cooperative dot
-// products, coalesced weight rows) -> exponential-race argmax.
-constexpr int SH_THREADS = 1024;
+// ---- the pieces of the sampling tail, each written once: LN_f of a row, the head's dot products, the row maximum, the
+// truncation threshold and the exponential race.  Every tail kernel below is made of these, so two kernels that form
+// the same quantity form the same bits.
+constexpr int SH_THREADS = 1024;  // one workgroup per token row
+constexpr int CP_ROWS = 4;        // the wave form: one wave per token row, CP_ROWS rows per workgroup
 
-template <int C, bool TRUNC = false, bool PER_SAMPLE = false>
-__device__ __forceinline__ void sample_row(float* lds, int row, const float* __restrict__ hidden,
-                                           const float* __restrict__ g, const float* __restrict__ bta,
-                                           const float* __restrict__ w, const float* __restrict__ expo, int head,
-                                           float temp, int64_t* __restrict__ x_t,
-                                           int64_t* __restrict__ out_idx, int n_class, int top_k = 0,
-                                           uint32_t top_p_q = 0) {
+// One wave, one C-wide row: lane l holds floats 4 l .. 4 l + 3 of every 256.
+template <int VPL>
+__device__ __forceinline__ void load_row(const float* p, int lane, f32x4 (&w)[VPL]) {
+#pragma unroll
+  for (int i = 0; i < VPL; ++i) w[i] = *reinterpret_cast<const f32x4*>(p + i * 256 + lane * 4);
+}
+// v = LN_f(xr), eps = 1e-5
+template <int C>
+__device__ __forceinline__ void lnf_row(const float* xr, const float* __restrict__ g, const float* __restrict__ bta,
+                                        int lane, f32x4 (&v)[C / 256]) {
   constexpr int VPL = C / 256;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float* xr = hidden + (int64_t)row * C;
-  f32x4 v[VPL];
+  load_row(xr, lane, v);
   float s = 0.f;
 #pragma unroll
-  for (int i = 0; i < VPL; ++i) {
-    v[i] = *reinterpret_cast<const f32x4*>(xr + i * 256 + lane * 4);
-    s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
-  }
+  for (int i = 0; i < VPL; ++i) s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
   const float mean = wave_sum(s) * (1.0f / C);
   float q = 0.f;
 #pragma unroll
@@ -232,31 +235,134 @@ __device__ __forceinline__ void sample_row(float* lds, int row, const float* __r
       q = fmaf(d, d, q);
     }
   const float rstd = 1.0f / sqrtf(wave_sum(q) * (1.0f / C) + 1e-5f);
+  f32x4 gg[VPL], bb[VPL];
+  load_row(g, lane, gg);
+  load_row(bta, lane, bb);
 #pragma unroll
-  for (int i = 0; i < VPL; ++i) {
-    const f32x4 gg = *reinterpret_cast<const f32x4*>(g + i * 256 + lane * 4);
-    const f32x4 bb = *reinterpret_cast<const f32x4*>(bta + i * 256 + lane * 4);
+  for (int i = 0; i < VPL; ++i)
 #pragma unroll
-    for (int e = 0; e < 4; ++e) v[i][e] = (v[i][e] - mean) * rstd * gg[e] + bb[e];
+    for (int e = 0; e < 4; ++e) v[i][e] = (v[i][e] - mean) * rstd * gg[i][e] + bb[i][e];
+}
+// This lane's share of <w, v>: one fma chain in element order (wave_sum of it is the logit)
+template <int VPL>
+__device__ __forceinline__ float lane_dot(const f32x4 (&w)[VPL], const f32x4 (&v)[VPL]) {
+  float t = 0.f;
+#pragma unroll
+  for (int i = 0; i < VPL; ++i)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) t = fmaf(w[i][e], v[i][e], t);
+  return t;
+}
+// acc[u] = this lane's share of <w[j0 + u], v>, u = 0 .. 3 (classes past the end repeat the last one): a wave takes 4
+// classes per iteration so that 8 independent 1-KiB weight-row loads are in flight (the loop is latency bound).  The
+// caller finishes each with wave_sum next to its guarded store.
+template <int C>
+__device__ __forceinline__ void head_dot4(const float* __restrict__ w, int j0, int n_class, int lane,
+                                          const f32x4 (&v)[C / 256], float (&acc)[4]) {
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    f32x4 ww[C / 256];
+    load_row(w + (int64_t)min(j0 + u, n_class - 1) * C, lane, ww);
+    acc[u] = lane_dot(ww, v);
   }
-  // logits: NW waves, each takes 4 classes per iteration so that 8 independent
-  // 1-KiB weight-row loads are in flight per wave (the loop is latency bound).
+}
+
+// Maximum over the NT threads of a row: a wave (NT == 64), or a workgroup through red[NT / 64].  The workgroup form
+// holds ONE barrier, after which everything the threads wrote to LDS before the call is visible as well.
+template <int NT>
+__device__ __forceinline__ float block_max(float mx, float* red, int lane, int wave) {
+  mx = wave_max(mx);
+  if constexpr (NT != 64) {
+    if (lane == 0) red[wave] = mx;
+    __syncthreads();
+    mx = red[0];
+#pragma unroll
+    for (int k = 1; k < NT / 64; ++k) mx = fmaxf(mx, red[k]);
+  }
+  return mx;
+}
+// thread t = 0 .. NT - 1 of the row owns lg[t], lg[t + NT], ...
+template <int NT>
+__device__ __forceinline__ float row_max(const float* lg, int n_class, int t, float* red, int lane, int wave) {
+  float mx = -INFINITY;
+  for (int j = t; j < n_class; j += NT) mx = fmaxf(mx, lg[j]);
+  return block_max<NT>(mx, red, lane, wave);
+}
+
+// theta of the row (class j enters the race iff lg[j] >= theta); -inf where nothing is cut.  The selection's LDS is one
+// object per workgroup, or one per wave in the wave form.
+template <int NT, bool TRUNC, bool PER_SAMPLE>
+__device__ __forceinline__ float row_theta(const float* lg, int n_class, float mx, int top_k, uint32_t top_p_q, int t) {
+  float theta = -INFINITY;
+  if constexpr (TRUNC) {
+    __shared__ trunc_lds tr[NT == 64 ? CP_ROWS : 1];
+    int kept;
+    if (!PER_SAMPLE || top_k != 0 || top_p_q != 0)  // (uniform over the wave / workgroup)
+      theta = trunc_unkey(trunc_select<NT>(lg, n_class, mx, top_k, top_p_q, &tr[NT == 64 ? threadIdx.x >> 6 : 0], t, &kept));
+  }
+  return theta;
+}
+
+// The exponential race: argmax_j exp(l_j - max) / q_j, the first index wins ties.
+struct race {
+  float best = -1.f;
+  int j = 0x7fffffff;
+  __device__ __forceinline__ void offer(float sc, int jj) {  // (a thread offers its classes in ascending order)
+    if (sc > best) {
+      best = sc;
+      j = jj;
+    }
+  }
+  __device__ __forceinline__ void wave_reduce() {  // every lane ends with the wave's winner
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ob = __shfl_xor(best, o, 64);
+      const int oj = __shfl_xor(j, o, 64);
+      if (ob > best || (ob == best && oj < j)) {
+        best = ob;
+        j = oj;
+      }
+    }
+  }
+  // after wave_reduce: the workgroup's winner, on thread 0 only.  red[] / redj[]: NW slots each; red[] may be the
+  // array block_max used (the first barrier: every thread has read it).
+  template <int NW>
+  __device__ __forceinline__ void block_reduce(float* red, int* redj, int tid) {
+    __syncthreads();
+    if ((tid & 63) == 0) {
+      red[tid >> 6] = best;
+      redj[tid >> 6] = j;
+    }
+    __syncthreads();
+    if (tid == 0)
+      for (int k = 1; k < NW; ++k)
+        if (red[k] > best || (red[k] == best && redj[k] < j)) {
+          best = red[k];
+          j = redj[k];
+        }
+  }
+  // all-NaN scores (only after a flagged split-precision overflow upstream): keep the token id
+  // inside the embedding table so the run reaches the host-side overflow check instead of faulting
+  __device__ __forceinline__ int winner(int n_class) const { return j >= n_class ? 0 : j; }
+};
+
+// One workgroup per token row; rows that are not (changed && of this head's
+// texture) exit at once.  LN_f -> 512->n_class head (wave-cooperative dot
+// products, coalesced weight rows) -> exponential-race argmax.
+template <int C, bool TRUNC = false, bool PER_SAMPLE = false>
+__device__ __forceinline__ void sample_row(float* lds, int row, const float* __restrict__ hidden,
+                                           const float* __restrict__ g, const float* __restrict__ bta,
+                                           const float* __restrict__ w, const float* __restrict__ expo, int head,
+                                           float temp, int64_t* __restrict__ x_t,
+                                           int64_t* __restrict__ out_idx, int n_class, int top_k = 0,
+                                           uint32_t top_p_q = 0) {
   constexpr int NW = SH_THREADS / 64;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  f32x4 v[C / 256];
+  lnf_row<C>(hidden + (int64_t)row * C, g, bta, lane, v);
   for (int j0 = wave * 4; j0 < n_class; j0 += NW * 4) {
     float acc[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int j = min(j0 + u, n_class - 1);
-      const float* wr = w + (int64_t)j * C;
-      float a = 0.f;
-#pragma unroll
-      for (int i = 0; i < VPL; ++i) {
-        const f32x4 ww = *reinterpret_cast<const f32x4*>(wr + i * 256 + lane * 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) a = fmaf(ww[e], v[i][e], a);
-      }
-      acc[u] = a;
-    }
+    head_dot4<C>(w, j0, n_class, lane, v, acc);
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const float r = wave_sum(acc[u]);
@@ -265,60 +371,19 @@ __device__ __forceinline__ void sample_row(float* lds, int row, const float* __r
   }
   __syncthreads();
   float* red = lds + n_class;
-  float mx = -INFINITY;
-  for (int j = tid; j < n_class; j += SH_THREADS) mx = fmaxf(mx, lds[j]);
-  mx = wave_max(mx);
-  if (lane == 0) red[wave] = mx;
-  __syncthreads();
-  mx = red[0];
-#pragma unroll
-  for (int k = 1; k < NW; ++k) mx = fmaxf(mx, red[k]);
-  float theta = -INFINITY;
-  if constexpr (TRUNC) {
-    __shared__ trunc_lds tr;
-    int kept;
-    if (!PER_SAMPLE || top_k != 0 || top_p_q != 0)  // (uniform over the workgroup)
-      theta = trunc_unkey(trunc_select<SH_THREADS>(lds, n_class, mx, top_k, top_p_q, &tr, tid, &kept));
-  }
-  // argmax_j exp(l_j - max) / q_j  (first index wins ties)
+  const float mx = row_max<SH_THREADS>(lds, n_class, tid, red, lane, wave);
+  const float theta = row_theta<SH_THREADS, TRUNC, PER_SAMPLE>(lds, n_class, mx, top_k, top_p_q, tid);
   const float* er = expo + (int64_t)row * n_class;
-  float best = -1.f;
-  int best_j = 0x7fffffff;
+  race best;
   for (int j = tid; j < n_class; j += SH_THREADS) {
     if (TRUNC && !(lds[j] >= theta)) continue;
-    const float sc = expf(lds[j] - mx) / er[j];
-    if (sc > best) {
-      best = sc;
-      best_j = j;
-    }
+    best.offer(expf(lds[j] - mx) / er[j], j);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ob = __shfl_xor(best, o, 64);
-    const int oj = __shfl_xor(best_j, o, 64);
-    if (ob > best || (ob == best && oj < best_j)) {
-      best = ob;
-      best_j = oj;
-    }
-  }
-  __syncthreads();
-  int* redj = reinterpret_cast<int*>(red + NW);
-  if (lane == 0) {
-    red[wave] = best;
-    redj[wave] = best_j;
-  }
-  __syncthreads();
+  best.wave_reduce();
+  best.block_reduce<NW>(red, reinterpret_cast<int*>(red + NW), tid);
   if (tid == 0) {
-    for (int k = 1; k < NW; ++k)
-      if (red[k] > best || (red[k] == best && redj[k] < best_j)) {
-        best = red[k];
-        best_j = redj[k];
-      }
-    // all-NaN scores (only after a flagged split-precision overflow upstream): keep the token id
-    // inside the embedding table so the run reaches the host-side overflow check instead of faulting
-    if (best_j >= n_class) best_j = 0;
-    x_t[row] = (int64_t)best_j + (int64_t)n_class * head;
-    out_idx[row] = best_j;
+    x_t[row] = (int64_t)best.winner(n_class) + (int64_t)n_class * head;
+    out_idx[row] = best.winner(n_class);
   }
 }
 
@@ -364,56 +429,19 @@ __global__ __launch_bounds__(SH_THREADS) void masked_ce_kernel(
     if (tid == 0) ce[row] = 0.f;
     return;
   }
-  constexpr int VPL = C / 256;
-  const float* xr = hidden + (int64_t)row * C;
-  f32x4 v[VPL];
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) {
-    v[i] = *reinterpret_cast<const f32x4*>(xr + i * 256 + lane * 4);
-    s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
-  }
-  const float mean = wave_sum(s) * (1.0f / C);
-  float q = 0.f;
-#pragma unroll
-  for (int i = 0; i < VPL; ++i)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float d = v[i][e] - mean;
-      q = fmaf(d, d, q);
-    }
-  const float rstd = 1.0f / sqrtf(wave_sum(q) * (1.0f / C) + 1e-5f);
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) {
-    const f32x4 gg = *reinterpret_cast<const f32x4*>(g + i * 256 + lane * 4);
-    const f32x4 bb = *reinterpret_cast<const f32x4*>(bta + i * 256 + lane * 4);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[i][e] = (v[i][e] - mean) * rstd * gg[e] + bb[e];
-  }
+  f32x4 v[C / 256];
+  lnf_row<C>(hidden + (int64_t)row * C, g, bta, lane, v);
   constexpr int NW = SH_THREADS / 64;
   const float* w = w_heads + (int64_t)head * n_class * C;
   for (int j = wave; j < n_class; j += NW) {
-    const float* wr = w + (int64_t)j * C;
-    float a = 0.f;
-#pragma unroll
-    for (int i = 0; i < VPL; ++i) {
-      const f32x4 ww = *reinterpret_cast<const f32x4*>(wr + i * 256 + lane * 4);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) a = fmaf(ww[e], v[i][e], a);
-    }
-    a = wave_sum(a);
+    f32x4 ww[C / 256];
+    load_row(w + (int64_t)j * C, lane, ww);
+    const float a = wave_sum(lane_dot(ww, v));
     if (lane == 0) lds[j] = a;
   }
   __syncthreads();
   float* red = lds + n_class;
-  float mx = -INFINITY;
-  for (int j = tid; j < n_class; j += SH_THREADS) mx = fmaxf(mx, lds[j]);
-  mx = wave_max(mx);
-  if (lane == 0) red[wave] = mx;
-  __syncthreads();
-  mx = red[0];
-#pragma unroll
-  for (int k = 1; k < NW; ++k) mx = fmaxf(mx, red[k]);
+  const float mx = row_max<SH_THREADS>(lds, n_class, tid, red, lane, wave);
   float se = 0.f;
   for (int j = tid; j < n_class; j += SH_THREADS) se += expf(lds[j] - mx);
   se = wave_sum(se);
@@ -473,7 +501,8 @@ __device__ __forceinline__ float aten_logf(float x) {
   const float t = __builtin_fmaf(y, cc, __builtin_fmaf(y, c, -r));
   return r + t;
 }
-__device__ __forceinline__ float torch_exponential_at(uint64_t seed, uint64_t offset, uint32_t grid_threads, uint64_t e) {
+// word of element e of a whole-tensor draw, and curand_uniform's (0, 1] value of a word
+__device__ __forceinline__ uint32_t torch_philox_word(uint64_t seed, uint64_t offset, uint32_t grid_threads, uint64_t e) {
   const uint64_t idx = e % grid_threads, m = e / grid_threads;
   const uint64_t ctr = offset / 4 + (m >> 2);
   uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)idx, (uint32_t)(idx >> 32)};
@@ -484,8 +513,13 @@ __device__ __forceinline__ float torch_exponential_at(uint64_t seed, uint64_t of
     k0 += 0x9E3779B9u;
     k1 += 0xBB67AE85u;
   }
-  const uint32_t v = c[m & 3];
-  const float u = __builtin_fmaf((float)v, 2.3283064365386963e-10f, 2.3283064365386963e-10f);  // (0, 1]
+  return c[m & 3];
+}
+__device__ __forceinline__ float philox_unit(uint32_t v) {
+  return __builtin_fmaf((float)v, 2.3283064365386963e-10f, 2.3283064365386963e-10f);  // (0, 1]
+}
+__device__ __forceinline__ float torch_exponential_at(uint64_t seed, uint64_t offset, uint32_t grid_threads, uint64_t e) {
+  const float u = philox_unit(torch_philox_word(seed, offset, grid_threads, e));
   const float lg = u >= 1.0f - 5.9604644775390625e-8f ? -5.9604644775390625e-8f : aten_logf(u);
   return -lg;
 }
@@ -501,18 +535,7 @@ __global__ void philox_exponential_kernel(uint64_t seed, uint64_t offset, uint32
 // transform (uniform_kernel of ATen/native/cuda/DistributionTemplates.h, from = 0, to = 1):
 // value = u * 1 + 0 with u = curand_uniform in (0, 1], and the bounds reversed: value == 1 -> 0.
 __device__ __forceinline__ float torch_uniform_at(uint64_t seed, uint64_t offset, uint32_t grid_threads, uint64_t e) {
-  const uint64_t idx = e % grid_threads, m = e / grid_threads;
-  const uint64_t ctr = offset / 4 + (m >> 2);
-  uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)idx, (uint32_t)(idx >> 32)};
-  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    philox_round(c, k0, k1);
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  const uint32_t v = c[m & 3];
-  const float u = __builtin_fmaf((float)v, 2.3283064365386963e-10f, 2.3283064365386963e-10f);  // (0, 1]
+  const float u = philox_unit(torch_philox_word(seed, offset, grid_threads, e));
   return u == 1.0f ? 0.0f : u;
 }
 
@@ -650,43 +673,19 @@ __global__ void schedule_advance_kernel(const int32_t* __restrict__ rows_tbl, co
 // per changed row streams 2 MB of head weights by itself (~50 us per step with ~16 rows on 16 CUs);
 // here SL_SPLIT workgroups per row take n_class / SL_SPLIT classes each (LN_f recomputed per
 // workgroup: 2 KB), then a second launch does max / exponential race over the row's logits.
-// Every logit is the same per-lane fma chain + wave butterfly as in sample_row, so the results are
-// bit-identical to the one-launch form.
+// Both forms take every logit from head_dot4 and draw through the same row_max / row_theta / race, so the results
+// are bit-identical to the one-launch form.
 constexpr int SL_SPLIT = 8, SL_THREADS = 256;
 
 template <int C, bool PER_SAMPLE>
 __global__ __launch_bounds__(SL_THREADS) void sample_logits_kernel(const t2h_sample_heads_args a, float* __restrict__ ws,
                                                                    const t2h_sample_params* __restrict__ params, int T) {
-  constexpr int VPL = C / 256;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int slot = blockIdx.x / SL_SPLIT, part = blockIdx.x - slot * SL_SPLIT;
   const int row = a.rows[slot];
   const int head = (int)a.tex[row];
-  const float* xr = a.hidden + (int64_t)(a.hidden_compact ? slot : row) * C;
-  f32x4 v[VPL];
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) {
-    v[i] = *reinterpret_cast<const f32x4*>(xr + i * 256 + lane * 4);
-    s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
-  }
-  const float mean = wave_sum(s) * (1.0f / C);
-  float q = 0.f;
-#pragma unroll
-  for (int i = 0; i < VPL; ++i)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float d = v[i][e] - mean;
-      q = fmaf(d, d, q);
-    }
-  const float rstd = 1.0f / sqrtf(wave_sum(q) * (1.0f / C) + 1e-5f);
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) {
-    const f32x4 gg = *reinterpret_cast<const f32x4*>(a.lnf_gamma + i * 256 + lane * 4);
-    const f32x4 bb = *reinterpret_cast<const f32x4*>(a.lnf_beta + i * 256 + lane * 4);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[i][e] = (v[i][e] - mean) * rstd * gg[e] + bb[e];
-  }
+  f32x4 v[C / 256];
+  lnf_row<C>(a.hidden + (int64_t)(a.hidden_compact ? slot : row) * C, a.lnf_gamma, a.lnf_beta, lane, v);
   const float temp = PER_SAMPLE ? params[row / T].temp : a.temp;
   const float* w = a.w_heads + (int64_t)head * a.n_class * C;
   const int per = (a.n_class + SL_SPLIT - 1) / SL_SPLIT;
@@ -694,19 +693,7 @@ __global__ __launch_bounds__(SL_THREADS) void sample_logits_kernel(const t2h_sam
   constexpr int NW = SL_THREADS / 64;
   for (int j0 = part * per + wave * 4; j0 < j_end; j0 += NW * 4) {
     float acc[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int j = min(j0 + u, a.n_class - 1);
-      const float* wr = w + (int64_t)j * C;
-      float t = 0.f;
-#pragma unroll
-      for (int i = 0; i < VPL; ++i) {
-        const f32x4 ww = *reinterpret_cast<const f32x4*>(wr + i * 256 + lane * 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) t = fmaf(ww[e], v[i][e], t);
-      }
-      acc[u] = t;
-    }
+    head_dot4<C>(w, j0, a.n_class, lane, v, acc);
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const float r = wave_sum(acc[u]);
@@ -724,28 +711,9 @@ __global__ __launch_bounds__(SH_THREADS) void sample_pick_kernel(const t2h_sampl
   const int slot = blockIdx.x, row = a.rows[slot];
   const int head = (int)a.tex[row];
   const float* lg = ws + (int64_t)slot * a.n_class;
-  float mx = -INFINITY;
-  for (int j = tid; j < a.n_class; j += SH_THREADS) mx = fmaxf(mx, lg[j]);
-  mx = wave_max(mx);
-  if (lane == 0) red[wave] = mx;
-  __syncthreads();
-  mx = red[0];
-#pragma unroll
-  for (int k = 1; k < NW; ++k) mx = fmaxf(mx, red[k]);
-  float theta = -INFINITY;
-  if constexpr (TRUNC) {
-    __shared__ trunc_lds tr;
-    int kept;
-    int top_k = a.top_k;
-    uint32_t top_p_q = a.top_p_q;
-    if constexpr (PER_SAMPLE) {
-      const sample_settings st = sample_settings_of(params, row, T, a.n_class);
-      top_k = st.top_k;
-      top_p_q = st.top_p_q;
-    }
-    if (!PER_SAMPLE || top_k != 0 || top_p_q != 0)  // (uniform over the workgroup)
-      theta = trunc_unkey(trunc_select<SH_THREADS>(lg, a.n_class, mx, top_k, top_p_q, &tr, tid, &kept));
-  }
+  const float mx = row_max<SH_THREADS>(lg, a.n_class, tid, red, lane, wave);
+  const sample_settings st = row_settings<PER_SAMPLE>(a.temp, a.top_k, a.top_p_q, params, row, T, a.n_class);
+  const float theta = row_theta<SH_THREADS, TRUNC, PER_SAMPLE>(lg, a.n_class, mx, st.top_k, st.top_p_q, tid);
   // noise of this row: explicit compact rows (expo_rows[expo_slot[slot]]), the head's explicit full
   // tensor, or computed -- at the row's own generator offset when the list mixes steps
   const float* er = a.expo_rows ? a.expo_rows + (int64_t)(a.expo_slot ? a.expo_slot[slot] : slot) * a.n_class
@@ -756,44 +724,19 @@ __global__ __launch_bounds__(SH_THREADS) void sample_pick_kernel(const t2h_sampl
   // the element of the reference's [n, n_class] draw this row owns: its row THERE (the host may have reordered the
   // samples of the batch, rng_rows) -- by default the row itself
   const int rng_row = a.rng_rows ? a.rng_rows[slot] : row;
-  float best = -1.f;
-  int best_j = 0x7fffffff;
+  race best;
   for (int j = tid; j < a.n_class; j += SH_THREADS) {
     if (TRUNC && !(lg[j] >= theta)) continue;
     const float q = er ? er[j]
                        : torch_exponential_at(pseed, poff, a.philox_grid_threads,
                                               (uint64_t)rng_row * a.n_class + j);
-    const float sc = expf(lg[j] - mx) / q;
-    if (sc > best) {
-      best = sc;
-      best_j = j;
-    }
+    best.offer(expf(lg[j] - mx) / q, j);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ob = __shfl_xor(best, o, 64);
-    const int oj = __shfl_xor(best_j, o, 64);
-    if (ob > best || (ob == best && oj < best_j)) {
-      best = ob;
-      best_j = oj;
-    }
-  }
-  __syncthreads();
-  int* redj = reinterpret_cast<int*>(red + NW);
-  if (lane == 0) {
-    red[wave] = best;
-    redj[wave] = best_j;
-  }
-  __syncthreads();
+  best.wave_reduce();
+  best.block_reduce<NW>(red, reinterpret_cast<int*>(red + NW), tid);
   if (tid == 0) {
-    for (int k = 1; k < NW; ++k)
-      if (red[k] > best || (red[k] == best && redj[k] < best_j)) {
-        best = red[k];
-        best_j = redj[k];
-      }
-    if (best_j >= a.n_class) best_j = 0;  // all-NaN scores: see sample_row
-    a.x_t[row] = (int64_t)best_j + (int64_t)a.n_class * head;
-    a.out_idx[(int64_t)head * a.n + row] = best_j;
+    a.x_t[row] = (int64_t)best.winner(a.n_class) + (int64_t)a.n_class * head;
+    a.out_idx[(int64_t)head * a.n + row] = best.winner(a.n_class);
   }
 }
 
@@ -807,8 +750,7 @@ __global__ __launch_bounds__(SH_THREADS) void sample_heads_kernel(const t2h_samp
   const int head = (int)a.tex[row];
   const float* expo = a.expo[head];
   if (expo == nullptr) return;  // cannot happen: a head with changed tokens always drew its noise
-  sample_settings st = {a.temp, a.top_k, a.top_p_q};
-  if constexpr (PER_SAMPLE) st = sample_settings_of(params, row, T, a.n_class);
+  const sample_settings st = row_settings<PER_SAMPLE>(a.temp, a.top_k, a.top_p_q, params, row, T, a.n_class);
   sample_row<C, TRUNC, PER_SAMPLE>(lds, row, a.hidden, a.lnf_gamma, a.lnf_beta, a.w_heads + (int64_t)head * a.n_class * C,
                                    expo, head, st.temp, a.x_t, a.out_idx + (int64_t)head * a.n, a.n_class, st.top_k,
                                    st.top_p_q);  // (full hidden only)
@@ -817,8 +759,8 @@ __global__ __launch_bounds__(SH_THREADS) void sample_heads_kernel(const t2h_samp
 // ---- confidence-ordered parallel decoding ("Confidence-ordered decoding").  A round samples EVERY masked
 // row -- up to B * 512 rows instead of a few dozen -- so the head GEMV of the tail above (2 MB of weights per row) is
 // the wrong shape: the masked rows are grouped by head, CT_ROWS rows of one head share one stream of its weights.
-// Every logit is still the per-lane fma chain + wave butterfly of sample_row (the LayerNorm'ed row now comes from LDS
-// instead of registers), so the logits, and the token the race draws, are the bits of t2h_sample_heads.
+// Every logit is still wave_sum(lane_dot) over the lnf_row'ed row (which now comes from LDS instead of registers), so the
+// logits, and the token the race draws, are the bits of t2h_sample_heads.
 constexpr int CT_ROWS = 16, CT_SPLIT = 4, CT_THREADS = 256, CT_HDR = 4;
 
 __host__ __device__ inline int conf_max_tiles(int n, int n_heads) { return (n + CT_ROWS - 1) / CT_ROWS + n_heads; }
@@ -860,8 +802,8 @@ __global__ __launch_bounds__(1024) void conf_group_kernel(const int64_t* __restr
   }
 }
 
-// One workgroup per (tile, class quarter): LN_f of the tile's rows into LDS (one wave per row, the arithmetic of
-// sample_row), then every wave streams 4 weight rows at a time and uses them for all rows of the tile.
+// One workgroup per (tile, class quarter): LN_f of the tile's rows into LDS (one wave per row), then every wave streams
+// 4 weight rows at a time and uses them for all rows of the tile.
 // PER_SAMPLE: the rows of a tile share a head, not an image -- the temperature is per ROW of the tile (lane r of
 // every wave holds row r's, read back with v_readlane: no LDS beyond xs, whose 32 KiB fit five times into a CU's).
 template <int C, bool PER_SAMPLE>
@@ -877,32 +819,10 @@ __global__ __launch_bounds__(CT_THREADS) void conf_logits_kernel(const t2h_confi
   const int head = td[0], cnt = min(td[2], CT_ROWS);
   const int32_t* rows = ws + CT_HDR + 3 * conf_max_tiles(a.n, a.n_heads) + td[1];
   for (int r = wave; r < cnt; r += NW) {
-    const float* xr = a.hidden + (int64_t)rows[r] * C;
     f32x4 v[VPL];
-    float s = 0.f;
+    lnf_row<C>(a.hidden + (int64_t)rows[r] * C, a.lnf_gamma, a.lnf_beta, lane, v);
 #pragma unroll
-    for (int i = 0; i < VPL; ++i) {
-      v[i] = *reinterpret_cast<const f32x4*>(xr + i * 256 + lane * 4);
-      s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
-    }
-    const float mean = wave_sum(s) * (1.0f / C);
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < VPL; ++i)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float d = v[i][e] - mean;
-        q = fmaf(d, d, q);
-      }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) * (1.0f / C) + 1e-5f);
-#pragma unroll
-    for (int i = 0; i < VPL; ++i) {
-      const f32x4 gg = *reinterpret_cast<const f32x4*>(a.lnf_gamma + i * 256 + lane * 4);
-      const f32x4 bb = *reinterpret_cast<const f32x4*>(a.lnf_beta + i * 256 + lane * 4);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[i][e] = (v[i][e] - mean) * rstd * gg[e] + bb[e];
-      *reinterpret_cast<f32x4*>(xs + r * C + i * 256 + lane * 4) = v[i];
-    }
+    for (int i = 0; i < VPL; ++i) *reinterpret_cast<f32x4*>(xs + r * C + i * 256 + lane * 4) = v[i];
   }
   __syncthreads();
   const float temp = a.temp;
@@ -916,25 +836,13 @@ __global__ __launch_bounds__(CT_THREADS) void conf_logits_kernel(const t2h_confi
   for (int j0 = part * per + wave * 4; j0 < j_end; j0 += NW * 4) {
     f32x4 ww[4][VPL];
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const float* wr = w + (int64_t)min(j0 + u, a.n_class - 1) * C;
-#pragma unroll
-      for (int i = 0; i < VPL; ++i) ww[u][i] = *reinterpret_cast<const f32x4*>(wr + i * 256 + lane * 4);
-    }
+    for (int u = 0; u < 4; ++u) load_row(w + (int64_t)min(j0 + u, a.n_class - 1) * C, lane, ww[u]);
     for (int r = 0; r < cnt; ++r) {
       f32x4 v[VPL];
-#pragma unroll
-      for (int i = 0; i < VPL; ++i) v[i] = *reinterpret_cast<const f32x4*>(xs + r * C + i * 256 + lane * 4);
+      load_row(xs + r * C, lane, v);
       float acc[4];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        float t = 0.f;
-#pragma unroll
-        for (int i = 0; i < VPL; ++i)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) t = fmaf(ww[u][i][e], v[i][e], t);
-        acc[u] = t;
-      }
+      for (int u = 0; u < 4; ++u) acc[u] = lane_dot(ww[u], v);
       float* lg = a.logits_ws + (int64_t)rows[r] * a.n_class;
       const float tr = PER_SAMPLE ? __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, row_temp), r))
                                   : temp;
@@ -947,9 +855,8 @@ __global__ __launch_bounds__(CT_THREADS) void conf_logits_kernel(const t2h_confi
   }
 }
 
-// One wave per row: max, the exponential race of sample_pick_kernel (same scores, lowest index of the maximum), the
-// sum of the same exponentials, and the log-probability of the drawn class.
-constexpr int CP_ROWS = 4;
+// One wave per row: max, the exponential race at the wave's scope (same scores, lowest index of the maximum), the sum
+// of the same exponentials, and the log-probability of the drawn class.
 template <bool TRUNC, bool PER_SAMPLE>
 __global__ __launch_bounds__(64 * CP_ROWS) void conf_pick_kernel(const t2h_confidence_tail_args a,
                                                                  const t2h_sample_params* __restrict__ params, int T) {
@@ -965,53 +872,30 @@ __global__ __launch_bounds__(64 * CP_ROWS) void conf_pick_kernel(const t2h_confi
     return;
   }
   const float* lg = a.logits_ws + (int64_t)row * a.n_class;
-  float mx = -INFINITY;
-  for (int j = lane; j < a.n_class; j += 64) mx = fmaxf(mx, lg[j]);
-  mx = wave_max(mx);
-  float theta = -INFINITY;
-  if constexpr (TRUNC) {  // only the token changes: se / conf below stay those of the full softmax
-    __shared__ trunc_lds tr[CP_ROWS];
-    int kept;
-    int top_k = a.top_k;
-    uint32_t top_p_q = a.top_p_q;
-    if constexpr (PER_SAMPLE) {
-      const sample_settings st = sample_settings_of(params, __builtin_amdgcn_readfirstlane(row), T, a.n_class);
-      top_k = st.top_k;
-      top_p_q = st.top_p_q;
-    }
-    if (!PER_SAMPLE || top_k != 0 || top_p_q != 0)  // (uniform over the wave)
-      theta = trunc_unkey(trunc_select<64>(lg, a.n_class, mx, top_k, top_p_q, &tr[threadIdx.x >> 6], lane, &kept));
-  }
+  const float mx = row_max<64>(lg, a.n_class, lane, nullptr, lane, 0);
+  const sample_settings st =
+      row_settings<PER_SAMPLE>(a.temp, a.top_k, a.top_p_q, params, __builtin_amdgcn_readfirstlane(row), T, a.n_class);
+  // only the token changes: se / conf below stay those of the full softmax
+  const float theta = row_theta<64, TRUNC, PER_SAMPLE>(lg, a.n_class, mx, st.top_k, st.top_p_q, lane);
   const float* er = a.expo ? a.expo + (int64_t)row * a.n_class : nullptr;
   const uint64_t pseed = a.philox_seed_dev ? *a.philox_seed_dev : a.philox_seed;
   const uint64_t poff = a.philox_offset_dev ? *a.philox_offset_dev : a.philox_offset;
-  float best = -1.f, se = 0.f;
-  int best_j = 0x7fffffff;
+  race best;
+  float se = 0.f;
   for (int j = lane; j < a.n_class; j += 64) {
     const float q = er ? er[j] : torch_exponential_at(pseed, poff, a.philox_grid_threads, (uint64_t)row * a.n_class + j);
     const float ex = expf(lg[j] - mx);
     const float sc = ex / q;
     se += ex;
     if (TRUNC && !(lg[j] >= theta)) continue;
-    if (sc > best) {
-      best = sc;
-      best_j = j;
-    }
+    best.offer(sc, j);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ob = __shfl_xor(best, o, 64);
-    const int oj = __shfl_xor(best_j, o, 64);
-    if (ob > best || (ob == best && oj < best_j)) {
-      best = ob;
-      best_j = oj;
-    }
-  }
+  best.wave_reduce();
   se = wave_sum(se);
   if (lane == 0) {
-    if (best_j >= a.n_class) best_j = 0;  // all-NaN scores: see sample_row
-    a.tok[row] = best_j;
-    a.conf[row] = (lg[best_j] - mx) - logf(se);
+    const int tok = best.winner(a.n_class);
+    a.tok[row] = tok;
+    a.conf[row] = (lg[tok] - mx) - logf(se);
   }
 }
 
@@ -1062,39 +946,28 @@ __global__ __launch_bounds__(CC_THREADS) void conf_commit_kernel(const t2h_confi
 }
 
 // ---- t2h_truncation_threshold: the selection alone, at the scope of sample_pick_kernel (one workgroup per row) or of
-// conf_pick_kernel (one wave per row); the row maximum is formed as those kernels form it.
+// conf_pick_kernel (one wave per row), with their row_max.
 template <int NT, bool PER_SAMPLE>
 __global__ __launch_bounds__(NT == 64 ? 64 * CP_ROWS : SH_THREADS) void trunc_threshold_kernel(
     const float* __restrict__ logits, int n_rows, int n_class, int top_k, uint32_t top_p_q, float* __restrict__ theta,
     int* __restrict__ kept, const t2h_sample_params* __restrict__ params, int T) {
-  constexpr int ROWS = NT == 64 ? CP_ROWS : 1, NW = NT / 64;
+  constexpr int ROWS = NT == 64 ? CP_ROWS : 1;
   __shared__ trunc_lds tr[ROWS];
   __shared__ float red[SH_THREADS / 64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int row = NT == 64 ? blockIdx.x * CP_ROWS + wave : blockIdx.x;
   if (row >= n_rows) return;  // (uniform over the wave; the workgroup form has one row per workgroup)
   const int t = NT == 64 ? lane : (int)threadIdx.x;
-  if constexpr (PER_SAMPLE) {
-    const sample_settings st = sample_settings_of(params, __builtin_amdgcn_readfirstlane(row), T, n_class);
-    top_k = st.top_k;
-    top_p_q = st.top_p_q;
-  }
+  const sample_settings st =
+      row_settings<PER_SAMPLE>(0.f, top_k, top_p_q, params, __builtin_amdgcn_readfirstlane(row), T, n_class);
+  const bool cut = st.top_k != 0 || st.top_p_q != 0;
   const float* lg = logits + (int64_t)row * n_class;
-  float mx = -INFINITY;
-  for (int j = t; j < n_class; j += NT) mx = fmaxf(mx, lg[j]);
-  mx = wave_max(mx);
-  if (NT != 64) {
-    if (lane == 0) red[wave] = mx;
-    __syncthreads();
-    mx = red[0];
-#pragma unroll
-    for (int k = 1; k < NW; ++k) mx = fmaxf(mx, red[k]);
-  }
+  const float mx = row_max<NT>(lg, n_class, t, red, lane, wave);
   int n_kept = n_class;
   uint32_t key = 0;
-  if (top_k != 0 || top_p_q != 0) key = trunc_select<NT>(lg, n_class, mx, top_k, top_p_q, &tr[NT == 64 ? wave : 0], t, &n_kept);
+  if (cut) key = trunc_select<NT>(lg, n_class, mx, st.top_k, st.top_p_q, &tr[NT == 64 ? wave : 0], t, &n_kept);
   if (t == 0) {
-    theta[row] = (top_k != 0 || top_p_q != 0) ? trunc_unkey(key) : -INFINITY;
+    theta[row] = cut ? trunc_unkey(key) : -INFINITY;
     kept[row] = n_kept;
   }
 }
@@ -1102,7 +975,7 @@ __global__ __launch_bounds__(NT == 64 ? 64 * CP_ROWS : SH_THREADS) void trunc_th
 // ---- sampled bottom-index refinement: routed_head_argmax_kernel of vq.hip with a draw in place of the
 // maximum.  One workgroup per token, the token's Cf features in LDS, thread t owns classes t, t + 256, ...: the logit of
 // a class is that kernel's serial fma chain + bias (the same float), divided by the temperature into LDS; then the row
-// maximum, the threshold of truncated sampling (the workgroup form of trunc_select) and conf_pick_kernel's race, noise
+// maximum, the threshold of truncated sampling (the workgroup form of trunc_select) and the race, noise
 // explicit or element (noise_row0 + row, j) of torch's whole-tensor exponential_ draw.
 constexpr int RS_THREADS = 256;
 template <bool TRUNC, bool PER_SAMPLE>
@@ -1123,15 +996,7 @@ __global__ __launch_bounds__(RS_THREADS) void routed_head_sample_kernel(const t2
     return;
   }
   const int t = (int)tex;
-  float temp = a.temp;
-  int top_k = a.top_k;
-  uint32_t top_p_q = a.top_p_q;
-  if constexpr (PER_SAMPLE) {
-    const sample_settings st = sample_settings_of(params, row, T, a.n_class);
-    temp = st.temp;
-    top_k = st.top_k;
-    top_p_q = st.top_p_q;
-  }
+  const sample_settings st = row_settings<PER_SAMPLE>(a.temp, a.top_k, a.top_p_q, params, row, T, a.n_class);
   for (int k = tid; k < a.Cf; k += RS_THREADS) fs[k] = a.feat[(int64_t)row * a.ldf + t * a.Cf + k];
   __syncthreads();
   float mx = -INFINITY;
@@ -1140,70 +1005,37 @@ __global__ __launch_bounds__(RS_THREADS) void routed_head_sample_kernel(const t2
     float acc = 0.f;
     for (int k = 0; k < a.Cf; ++k) acc = fmaf(wr[k], fs[k], acc);
     acc += a.b[t * a.n_class + j];
-    const float l = acc / temp;
+    const float l = acc / st.temp;
     lg[j] = l;
     if (a.logits_ws) a.logits_ws[(int64_t)row * a.n_class + j] = l;
     mx = fmaxf(mx, l);
   }
-  mx = wave_max(mx);
-  if (lane == 0) red[wave] = mx;
-  __syncthreads();  // (also: every logit of the row is in LDS)
-  mx = red[0];
-#pragma unroll
-  for (int k = 1; k < NW; ++k) mx = fmaxf(mx, red[k]);
-  float theta = -INFINITY;
-  if constexpr (TRUNC) {  // only the token changes: se / logp below stay those of the full softmax
-    __shared__ trunc_lds tr;
-    int kept;
-    if (!PER_SAMPLE || top_k != 0 || top_p_q != 0)  // (uniform over the workgroup)
-      theta = trunc_unkey(trunc_select<RS_THREADS>(lg, a.n_class, mx, top_k, top_p_q, &tr, tid, &kept));
-  }
+  mx = block_max<RS_THREADS>(mx, red, lane, wave);  // (its barrier also publishes lg[]: every logit of the row is in LDS)
+  // only the token changes: se / logp below stay those of the full softmax
+  const float theta = row_theta<RS_THREADS, TRUNC, PER_SAMPLE>(lg, a.n_class, mx, st.top_k, st.top_p_q, tid);
   const float* er = a.expo ? a.expo + (int64_t)row * a.n_class : nullptr;
   const uint64_t e0 = (uint64_t)(a.noise_row0 + row) * (uint64_t)a.n_class;
-  float best = -1.f, se = 0.f;
-  int best_j = 0x7fffffff;
+  race best;
+  float se = 0.f;
   for (int j = tid; j < a.n_class; j += RS_THREADS) {
     const float q = er ? er[j] : torch_exponential_at(a.philox_seed, a.philox_offset, a.philox_grid_threads, e0 + j);
     const float ex = expf(lg[j] - mx);
     const float sc = ex / q;
     se += ex;
     if (TRUNC && !(lg[j] >= theta)) continue;
-    if (sc > best) {
-      best = sc;
-      best_j = j;
-    }
+    best.offer(sc, j);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ob = __shfl_xor(best, o, 64);
-    const int oj = __shfl_xor(best_j, o, 64);
-    if (ob > best || (ob == best && oj < best_j)) {
-      best = ob;
-      best_j = oj;
-    }
-  }
+  best.wave_reduce();
   se = wave_sum(se);
   float* reds = red + NW;
-  int* redj = reinterpret_cast<int*>(red + 2 * NW);
-  __syncthreads();  // (red[] has been read by every thread)
-  if (lane == 0) {
-    red[wave] = best;
-    reds[wave] = se;
-    redj[wave] = best_j;
-  }
-  __syncthreads();
+  if (lane == 0) reds[wave] = se;  // (slots of its own: published by block_reduce's barriers)
+  best.block_reduce<NW>(red, reinterpret_cast<int*>(red + 2 * NW), tid);
   if (tid == 0) {
     se = reds[0];
-    for (int k = 1; k < NW; ++k) {
-      se += reds[k];
-      if (red[k] > best || (red[k] == best && redj[k] < best_j)) {
-        best = red[k];
-        best_j = redj[k];
-      }
-    }
-    if (best_j >= a.n_class) best_j = 0;  // all-NaN scores: see sample_row
-    a.out_lists[(int64_t)t * a.n + row] = best_j;
-    if (a.logp) a.logp[row] = (lg[best_j] - mx) - logf(se);
+    for (int k = 1; k < NW; ++k) se += reds[k];
+    const int tok = best.winner(a.n_class);
+    a.out_lists[(int64_t)t * a.n + row] = tok;
+    if (a.logp) a.logp[row] = (lg[tok] - mx) - logf(se);
   }
 }
 }  // namespace
@@ -1225,6 +1057,11 @@ static inline bool trunc_settings(int32_t n_class, int32_t* top_k, uint32_t* top
   T2H_REQUIRE((params) != nullptr && (T) > 0 && (n) % (T) == 0 && (a_n_class) <= 2048,                                 \
               name ": params[n / rows_per_sample] expected, rows_per_sample=%d dividing n=%d; n_class <= 2048", (int)(T), \
               (int)(n))
+
+// The instance of a <[...,] TRUNC, PER_SAMPLE> tail kernel for a launch: PER_SAMPLE for a table (`params`), else the
+// scalars' instance with or without the truncation code (`trunc`).  Leading template arguments follow the name.
+#define T2H_TAIL_KERNEL(kernel, ...)                                                                                  \
+  (params ? kernel<__VA_ARGS__ true, true> : trunc ? kernel<__VA_ARGS__ true, false> : kernel<__VA_ARGS__ false, false>)
 
 template <bool PER_SAMPLE>
 static int trunc_threshold_launch(const float* logits, int32_t n_rows, int32_t n_class, int32_t top_k, uint32_t top_p_q,
@@ -1283,13 +1120,8 @@ extern "C" int t2h_routed_head_sample(const t2h_routed_sample_args* args, const 
   }
   const bool trunc = trunc_settings(a.n_class, &a.top_k, &a.top_p_q);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (params)
-    hipLaunchKernelGGL((routed_head_sample_kernel<true, true>), dim3(a.n), dim3(RS_THREADS), lds, s, a, params,
-                       rows_per_sample);
-  else if (trunc)
-    hipLaunchKernelGGL((routed_head_sample_kernel<true, false>), dim3(a.n), dim3(RS_THREADS), lds, s, a, params, 0);
-  else
-    hipLaunchKernelGGL((routed_head_sample_kernel<false, false>), dim3(a.n), dim3(RS_THREADS), lds, s, a, params, 0);
+  hipLaunchKernelGGL(T2H_TAIL_KERNEL(routed_head_sample_kernel, ), dim3(a.n), dim3(RS_THREADS), lds, s, a, params,
+                     params ? rows_per_sample : 0);
   T2H_CHECK_LAUNCH("t2h_routed_head_sample");
   return T2H_OK;
 }
@@ -1320,17 +1152,10 @@ static int confidence_tail_launch(const t2h_confidence_tail_args* args, const t2
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(conf_group_kernel, dim3(1), dim3(1024), 0, s, a.x_t, a.tex, a.mask_id, a.n, a.n_heads, a.group_ws);
   const dim3 lgrid(conf_max_tiles(a.n, a.n_heads) * CT_SPLIT), pgrid((a.n + CP_ROWS - 1) / CP_ROWS);
-  if (params) {
-    T2H_PER_SAMPLE_REQUIRE("t2h_confidence_tail_per_sample", params, T, a.n, a.n_class);
-    hipLaunchKernelGGL((conf_logits_kernel<512, true>), lgrid, dim3(CT_THREADS), 0, s, a, params, T);
-    hipLaunchKernelGGL((conf_pick_kernel<true, true>), pgrid, dim3(64 * CP_ROWS), 0, s, a, params, T);
-  } else {
-    hipLaunchKernelGGL((conf_logits_kernel<512, false>), lgrid, dim3(CT_THREADS), 0, s, a, params, T);
-    if (trunc)
-      hipLaunchKernelGGL((conf_pick_kernel<true, false>), pgrid, dim3(64 * CP_ROWS), 0, s, a, params, T);
-    else
-      hipLaunchKernelGGL((conf_pick_kernel<false, false>), pgrid, dim3(64 * CP_ROWS), 0, s, a, params, T);
-  }
+  if (params) T2H_PER_SAMPLE_REQUIRE("t2h_confidence_tail_per_sample", params, T, a.n, a.n_class);
+  hipLaunchKernelGGL((params ? conf_logits_kernel<512, true> : conf_logits_kernel<512, false>), lgrid, dim3(CT_THREADS), 0,
+                     s, a, params, T);
+  hipLaunchKernelGGL(T2H_TAIL_KERNEL(conf_pick_kernel, ), pgrid, dim3(64 * CP_ROWS), 0, s, a, params, T);
   T2H_CHECK_LAUNCH("t2h_confidence_tail");
   return T2H_OK;
 }
@@ -1437,26 +1262,14 @@ static int sample_heads_launch(const t2h_sample_heads_args* args, const t2h_samp
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (a.logits_ws) {  // two launches, SL_SPLIT workgroups per row stream the head weights
     const dim3 lgrid(a.n_rows * SL_SPLIT), pgrid(a.n_rows);
-    if (params) {
-      hipLaunchKernelGGL((sample_logits_kernel<512, true>), lgrid, dim3(SL_THREADS), 0, s, a, a.logits_ws, params, T);
-      hipLaunchKernelGGL((sample_pick_kernel<true, true>), pgrid, dim3(SH_THREADS), 0, s, a, a.logits_ws, params, T);
-    } else {
-      hipLaunchKernelGGL((sample_logits_kernel<512, false>), lgrid, dim3(SL_THREADS), 0, s, a, a.logits_ws, params, T);
-      if (trunc)
-        hipLaunchKernelGGL((sample_pick_kernel<true, false>), pgrid, dim3(SH_THREADS), 0, s, a, a.logits_ws, params, T);
-      else
-        hipLaunchKernelGGL((sample_pick_kernel<false, false>), pgrid, dim3(SH_THREADS), 0, s, a, a.logits_ws, params, T);
-    }
+    hipLaunchKernelGGL((params ? sample_logits_kernel<512, true> : sample_logits_kernel<512, false>), lgrid,
+                       dim3(SL_THREADS), 0, s, a, a.logits_ws, params, T);
+    hipLaunchKernelGGL(T2H_TAIL_KERNEL(sample_pick_kernel, ), pgrid, dim3(SH_THREADS), 0, s, a, a.logits_ws, params, T);
     T2H_CHECK_LAUNCH("t2h_sample_heads");
     return T2H_OK;
   }
   const size_t lds = (size_t)(a.n_class + 2 * (SH_THREADS / 64)) * sizeof(float);
-  if (params)
-    hipLaunchKernelGGL((sample_heads_kernel<512, true, true>), dim3(a.n_rows), dim3(SH_THREADS), lds, s, a, params, T);
-  else if (trunc)
-    hipLaunchKernelGGL((sample_heads_kernel<512, true, false>), dim3(a.n_rows), dim3(SH_THREADS), lds, s, a, params, T);
-  else
-    hipLaunchKernelGGL((sample_heads_kernel<512, false, false>), dim3(a.n_rows), dim3(SH_THREADS), lds, s, a, params, T);
+  hipLaunchKernelGGL(T2H_TAIL_KERNEL(sample_heads_kernel, 512, ), dim3(a.n_rows), dim3(SH_THREADS), lds, s, a, params, T);
   T2H_CHECK_LAUNCH("t2h_sample_heads");
   return T2H_OK;
 }
@@ -1519,32 +1332,36 @@ extern "C" int t2h_philox_uniform_f32(uint64_t seed, uint64_t offset, uint32_t g
   return T2H_OK;
 }
 
+// keep == NULL: t2h_unmask_schedule; else the KEEP instance.  `name`: the entry point, for its error texts.
+static int unmask_schedule_launch(const char* name, uint64_t seed, uint64_t offset, uint32_t rand_grid_threads,
+                                  uint32_t rand_inc, uint32_t expo_inc, const int64_t* tex, const uint8_t* keep, int32_t n,
+                                  int32_t steps, int32_t n_heads, int32_t* step_of_row, uint32_t* head_mask,
+                                  void* stream) {
+  T2H_REQUIRE(tex && step_of_row && head_mask, "%s: NULL pointer", name);
+  T2H_REQUIRE(n > 0 && steps >= 1 && steps <= SCHED_MAX_STEPS && n_heads > 0 && n_heads <= T2H_MAX_HEADS &&
+                  rand_grid_threads > 0 && offset % 4 == 0 && rand_inc % 4 == 0 && expo_inc % 4 == 0,
+              "%s: bad arguments (n=%d steps=%d n_heads=%d)", name, n, steps, n_heads);
+  hipLaunchKernelGGL((keep ? unmask_schedule_kernel<true> : unmask_schedule_kernel<false>), dim3(1), dim3(SCHED_THREADS), 0,
+                     static_cast<hipStream_t>(stream), seed, offset, rand_grid_threads, rand_inc, expo_inc, tex, keep, n,
+                     steps, step_of_row, head_mask);
+  T2H_CHECK_LAUNCH(name);
+  return T2H_OK;
+}
+
 extern "C" int t2h_unmask_schedule(uint64_t seed, uint64_t offset, uint32_t rand_grid_threads, uint32_t rand_inc,
                                    uint32_t expo_inc, const int64_t* tex, int32_t n, int32_t steps, int32_t n_heads,
                                    int32_t* step_of_row, uint32_t* head_mask, void* stream) {
-  T2H_REQUIRE(tex && step_of_row && head_mask, "t2h_unmask_schedule: NULL pointer");
-  T2H_REQUIRE(n > 0 && steps >= 1 && steps <= SCHED_MAX_STEPS && n_heads > 0 && n_heads <= T2H_MAX_HEADS &&
-                  rand_grid_threads > 0 && offset % 4 == 0 && rand_inc % 4 == 0 && expo_inc % 4 == 0,
-              "t2h_unmask_schedule: bad arguments (n=%d steps=%d n_heads=%d)", n, steps, n_heads);
-  hipLaunchKernelGGL(unmask_schedule_kernel<false>, dim3(1), dim3(SCHED_THREADS), 0, static_cast<hipStream_t>(stream),
-                     seed, offset, rand_grid_threads, rand_inc, expo_inc, tex, (const uint8_t*)nullptr, n, steps,
-                     step_of_row, head_mask);
-  T2H_CHECK_LAUNCH("t2h_unmask_schedule");
-  return T2H_OK;
+  return unmask_schedule_launch("t2h_unmask_schedule", seed, offset, rand_grid_threads, rand_inc, expo_inc, tex, nullptr,
+                                n, steps, n_heads, step_of_row, head_mask, stream);
 }
 
 extern "C" int t2h_unmask_schedule_keep(uint64_t seed, uint64_t offset, uint32_t rand_grid_threads, uint32_t rand_inc,
                                         uint32_t expo_inc, const int64_t* tex, const uint8_t* keep, int32_t n,
                                         int32_t steps, int32_t n_heads, int32_t* step_of_row, uint32_t* head_mask,
                                         void* stream) {
-  T2H_REQUIRE(tex && keep && step_of_row && head_mask, "t2h_unmask_schedule_keep: NULL pointer");
-  T2H_REQUIRE(n > 0 && steps >= 1 && steps <= SCHED_MAX_STEPS && n_heads > 0 && n_heads <= T2H_MAX_HEADS &&
-                  rand_grid_threads > 0 && offset % 4 == 0 && rand_inc % 4 == 0 && expo_inc % 4 == 0,
-              "t2h_unmask_schedule_keep: bad arguments (n=%d steps=%d n_heads=%d)", n, steps, n_heads);
-  hipLaunchKernelGGL(unmask_schedule_kernel<true>, dim3(1), dim3(SCHED_THREADS), 0, static_cast<hipStream_t>(stream),
-                     seed, offset, rand_grid_threads, rand_inc, expo_inc, tex, keep, n, steps, step_of_row, head_mask);
-  T2H_CHECK_LAUNCH("t2h_unmask_schedule_keep");
-  return T2H_OK;
+  T2H_REQUIRE(keep != nullptr, "t2h_unmask_schedule_keep: NULL pointer");
+  return unmask_schedule_launch("t2h_unmask_schedule_keep", seed, offset, rand_grid_threads, rand_inc, expo_inc, tex, keep,
+                                n, steps, n_heads, step_of_row, head_mask, stream);
 }
 
 extern "C" int t2h_edit_prefill(const int64_t* src_lists, const int64_t* tex, const uint8_t* keep, int64_t mask_id,
