@@ -359,6 +359,13 @@ typedef struct t2h_sample_heads_args {
    * (the kernels without it) */
   int32_t top_k;
   uint32_t top_p_q;
+  /* optional [n], indexed by token row like x_t (NULL = off: the kernels without it): logp[row] = the natural-log
+   * probability of the token the row drew under the FULL softmax of its temperature-scaled logits l,
+   *   logp = (l_tok - max l) - logf(se),  se = sum_j expf(l_j - max l)  over all n_class classes
+   * (thread t of the row's 1024 adds its classes t, t + 1024, ... in ascending order, then the wave butterfly, then the
+   * 16 waves in wave order: both forms of the tail give the same bits).  Truncation changes the token, never the
+   * distribution.  Rows that are not listed are not written; a row listed twice is written twice with the same value. */
+  float* logp;
 } t2h_sample_heads_args;
 /* max |x| as the bits of the fp32 maximum, atomicMax'ed into *out_bits (the caller zeroes it; uint order = float order
  * for non-negative values, so the result does not depend on the order of the updates): of an fp32 matrix, and of the
@@ -480,6 +487,7 @@ typedef struct t2h_confidence_commit_args {
   int64_t* out;             /* [n_heads][B * T] */
   float* scores;
   int32_t B, T, n_heads, n_class;
+  float* logp;              /* optional [B * T]: a committed row gets logp[row] = conf[row] (a copy); others are not written */
 } t2h_confidence_commit_args;
 int64_t t2h_confidence_group_ws_ints(int32_t n, int32_t n_heads);
 int t2h_confidence_tail(const t2h_confidence_tail_args* args, void* stream);
@@ -523,6 +531,13 @@ int t2h_confidence_commit_per_sample(const t2h_confidence_commit_args* args, voi
 int t2h_truncation_threshold_per_row(const float* logits, int32_t n_rows, int32_t n_class,
                                      const t2h_sample_params* params, int32_t rows_per_sample, int32_t scope,
                                      float* theta, int32_t* kept, void* stream);
+
+/* Per-image summary of a run's per-token log-probabilities (logp [B][T] as the sampling tails write it; NaN = the row
+ * was never drawn and is skipped): sum[b], count[b] = the number of drawn rows, min[b].  One workgroup per image on a
+ * reduction tree that depends on T alone (thread t of 256: rows t, t + 256, ... ascending; wave butterfly; the four
+ * waves in order), so an image's numbers have the same bits wherever it sits in a batch.  An image without a drawn
+ * row: sum 0, count 0, min +inf. */
+int t2h_logp_summary(const float* logp, int32_t B, int32_t T, float* sum, int32_t* count, float* min, void* stream);
 
 /* Sampler training-time forward (models/transformer_model.py:212-274, forward only).
  * q_sample: mask[b,i] = u[b,i] < t[b] / num_timesteps; x_t = mask ? mask_id : x0.

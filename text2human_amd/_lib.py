@@ -62,6 +62,7 @@ class SampleHeadsArgs(ctypes.Structure):
         ('row_philox_offset', c_vp), ('expo_rows', c_vp), ('expo_slot', c_vp), ('philox_seed_dev', c_vp),
         ('rng_rows', c_vp),
         ('top_k', c_i32), ('top_p_q', ctypes.c_uint32),
+        ('logp', c_vp),
     ]
 
 
@@ -85,6 +86,7 @@ class ConfidenceCommitArgs(ctypes.Structure):
         ('philox_seed_dev', c_vp), ('philox_offset_dev', c_vp), ('philox_grid_threads', ctypes.c_uint32),
         ('k', c_vp), ('tau', c_vp), ('mask_id', c_i64), ('x_t', c_vp), ('out', c_vp), ('scores', c_vp),
         ('B', c_i32), ('T', c_i32), ('n_heads', c_i32), ('n_class', c_i32),
+        ('logp', c_vp),
     ]
 
 
@@ -147,6 +149,7 @@ SIGNATURES = {
     't2h_confidence_group_ws_ints': (c_i64, [c_i32, c_i32]),
     't2h_confidence_tail': (ctypes.c_int, [ctypes.POINTER(ConfidenceTailArgs), c_vp]),
     't2h_confidence_commit': (ctypes.c_int, [ctypes.POINTER(ConfidenceCommitArgs), c_vp]),
+    't2h_logp_summary': (ctypes.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     't2h_truncation_threshold': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, ctypes.c_uint32, c_i32, c_vp, c_vp, c_vp]),
     't2h_sample_heads_per_sample': (ctypes.c_int, [ctypes.POINTER(SampleHeadsArgs), c_vp, c_i32, c_vp]),
     't2h_confidence_tail_per_sample': (ctypes.c_int, [ctypes.POINTER(ConfidenceTailArgs), c_vp, c_i32, c_vp]),

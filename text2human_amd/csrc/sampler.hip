@@ -289,6 +289,26 @@ __device__ __forceinline__ float row_max(const float* lg, int n_class, int t, fl
   return block_max<NT>(mx, red, lane, wave);
 }
 
+// se = sum_j expf(lg[j] - mx) over ALL classes of the row, in an order that is part of the definition: thread t adds its
+// classes t, t + NT, ... in ascending order, wave_sum, and (NT != 64) the waves' sums are added in wave order through
+// reds[NT / 64].  Every thread returns the sum.  The workgroup form holds one barrier before its LDS writes (whoever
+// read reds[] before the call has finished) and one after them.  log p(tok) = (lg[tok] - mx) - logf(se).
+template <int NT>
+__device__ __forceinline__ float row_logsum(const float* lg, int n_class, float mx, int t, float* reds, int lane, int wave) {
+  float se = 0.f;
+  for (int j = t; j < n_class; j += NT) se += expf(lg[j] - mx);
+  se = wave_sum(se);
+  if constexpr (NT != 64) {
+    __syncthreads();
+    if (lane == 0) reds[wave] = se;
+    __syncthreads();
+    se = reds[0];
+#pragma unroll
+    for (int k = 1; k < NT / 64; ++k) se += reds[k];
+  }
+  return se;
+}
+
 // theta of the row (class j enters the race iff lg[j] >= theta); -inf where nothing is cut.  The selection's LDS is one
 // object per workgroup, or one per wave in the wave form.
 template <int NT, bool TRUNC, bool PER_SAMPLE>
@@ -349,13 +369,13 @@ struct race {
 // One workgroup per token row; rows that are not (changed && of this head's
 // texture) exit at once.  LN_f -> 512->n_class head (wave-cooperative dot
 // products, coalesced weight rows) -> exponential-race argmax.
-template <int C, bool TRUNC = false, bool PER_SAMPLE = false>
+template <int C, bool TRUNC = false, bool PER_SAMPLE = false, bool LOGP = false>
 __device__ __forceinline__ void sample_row(float* lds, int row, const float* __restrict__ hidden,
                                            const float* __restrict__ g, const float* __restrict__ bta,
                                            const float* __restrict__ w, const float* __restrict__ expo, int head,
                                            float temp, int64_t* __restrict__ x_t,
                                            int64_t* __restrict__ out_idx, int n_class, int top_k = 0,
-                                           uint32_t top_p_q = 0) {
+                                           uint32_t top_p_q = 0, float* __restrict__ logp = nullptr) {
   constexpr int NW = SH_THREADS / 64;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   f32x4 v[C / 256];
@@ -384,6 +404,10 @@ __device__ __forceinline__ void sample_row(float* lds, int row, const float* __r
   if (tid == 0) {
     x_t[row] = (int64_t)best.winner(n_class) + (int64_t)n_class * head;
     out_idx[row] = best.winner(n_class);
+  }
+  if constexpr (LOGP) {  // (after the race: its barrier frees red[] once thread 0 has read the winner)
+    const float se = row_logsum<SH_THREADS>(lds, n_class, mx, tid, red, lane, wave);
+    if (tid == 0) logp[row] = (lds[best.winner(n_class)] - mx) - logf(se);
   }
 }
 
@@ -702,7 +726,7 @@ __global__ __launch_bounds__(SL_THREADS) void sample_logits_kernel(const t2h_sam
   }
 }
 
-template <bool TRUNC, bool PER_SAMPLE>
+template <bool TRUNC, bool PER_SAMPLE, bool LOGP>
 __global__ __launch_bounds__(SH_THREADS) void sample_pick_kernel(const t2h_sample_heads_args a, const float* __restrict__ ws,
                                                                  const t2h_sample_params* __restrict__ params, int T) {
   __shared__ float red[2 * (SH_THREADS / 64)];
@@ -738,11 +762,15 @@ __global__ __launch_bounds__(SH_THREADS) void sample_pick_kernel(const t2h_sampl
     a.x_t[row] = (int64_t)best.winner(a.n_class) + (int64_t)a.n_class * head;
     a.out_idx[(int64_t)head * a.n + row] = best.winner(a.n_class);
   }
+  if constexpr (LOGP) {  // (after the race: its barrier frees red[] once thread 0 has read the winner)
+    const float se = row_logsum<SH_THREADS>(lg, a.n_class, mx, tid, red, lane, wave);
+    if (tid == 0) a.logp[row] = (lg[best.winner(a.n_class)] - mx) - logf(se);
+  }
 }
 
 // All heads in one launch: one workgroup per CHANGED token (compact list from
 // unmask_step), which picks the head / noise tensor of its own texture.
-template <int C, bool TRUNC, bool PER_SAMPLE>
+template <int C, bool TRUNC, bool PER_SAMPLE, bool LOGP>
 __global__ __launch_bounds__(SH_THREADS) void sample_heads_kernel(const t2h_sample_heads_args a,
                                                                   const t2h_sample_params* __restrict__ params, int T) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -751,9 +779,10 @@ __global__ __launch_bounds__(SH_THREADS) void sample_heads_kernel(const t2h_samp
   const float* expo = a.expo[head];
   if (expo == nullptr) return;  // cannot happen: a head with changed tokens always drew its noise
   const sample_settings st = row_settings<PER_SAMPLE>(a.temp, a.top_k, a.top_p_q, params, row, T, a.n_class);
-  sample_row<C, TRUNC, PER_SAMPLE>(lds, row, a.hidden, a.lnf_gamma, a.lnf_beta, a.w_heads + (int64_t)head * a.n_class * C,
-                                   expo, head, st.temp, a.x_t, a.out_idx + (int64_t)head * a.n, a.n_class, st.top_k,
-                                   st.top_p_q);  // (full hidden only)
+  sample_row<C, TRUNC, PER_SAMPLE, LOGP>(lds, row, a.hidden, a.lnf_gamma, a.lnf_beta,
+                                         a.w_heads + (int64_t)head * a.n_class * C, expo, head, st.temp, a.x_t,
+                                         a.out_idx + (int64_t)head * a.n, a.n_class, st.top_k, st.top_p_q,
+                                         a.logp);  // (full hidden only)
 }
 
 // ---- confidence-ordered parallel decoding ("Confidence-ordered decoding").  A round samples EVERY masked
@@ -941,7 +970,54 @@ __global__ __launch_bounds__(CC_THREADS) void conf_commit_kernel(const t2h_confi
       const int64_t tk = a.tok[row], h = a.tex[row];
       a.x_t[row] = tk + (int64_t)a.n_class * h;
       a.out[h * ((int64_t)a.B * T) + row] = tk;
+      if (a.logp) a.logp[row] = a.conf[row];  // (a copy: the log-probability the tail formed for the committed token)
     }
+  }
+}
+
+// ---- t2h_logp_summary: per image, the sum / count / minimum of the log-probabilities of its drawn rows (NaN = never
+// drawn: skipped).  One workgroup per image on a tree that depends on T alone: thread t takes rows t, t + 256, ... in
+// ascending order, then the wave butterfly, then the four waves in wave order -- an image's three numbers do not depend
+// on where it sits in the batch.
+constexpr int LS_THREADS = 256;
+__global__ __launch_bounds__(LS_THREADS) void logp_summary_kernel(const float* __restrict__ logp, int T,
+                                                                  float* __restrict__ sum, int32_t* __restrict__ count,
+                                                                  float* __restrict__ mn) {
+  constexpr int NW = LS_THREADS / 64;
+  __shared__ float red_s[NW], red_m[NW];
+  __shared__ int red_c[NW];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float* lp = logp + (int64_t)b * T;
+  float s = 0.f, m = INFINITY;
+  int c = 0;
+  for (int i = tid; i < T; i += LS_THREADS) {
+    const float v = lp[i];
+    if (v != v) continue;
+    s += v;
+    m = fminf(m, v);
+    ++c;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    s += __shfl_xor(s, o, 64);
+    m = fminf(m, __shfl_xor(m, o, 64));
+    c += __shfl_xor(c, o, 64);
+  }
+  if (lane == 0) {
+    red_s[wave] = s;
+    red_m[wave] = m;
+    red_c[wave] = c;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    for (int k = 1; k < NW; ++k) {
+      s += red_s[k];
+      m = fminf(m, red_m[k]);
+      c += red_c[k];
+    }
+    sum[b] = s;
+    count[b] = c;
+    mn[b] = m;
   }
 }
 
@@ -1062,6 +1138,14 @@ static inline bool trunc_settings(int32_t n_class, int32_t* top_k, uint32_t* top
 // scalars' instance with or without the truncation code (`trunc`).  Leading template arguments follow the name.
 #define T2H_TAIL_KERNEL(kernel, ...)                                                                                  \
   (params ? kernel<__VA_ARGS__ true, true> : trunc ? kernel<__VA_ARGS__ true, false> : kernel<__VA_ARGS__ false, false>)
+// The same for a <[...,] TRUNC, PER_SAMPLE, LOGP> kernel: the LOGP = false instances (the code without the log-sum) unless
+// the launch has a `logp` output.
+#define T2H_TAIL_KERNEL_L(kernel, LOGP, ...)                                                                          \
+  (params  ? kernel<__VA_ARGS__ true, true, LOGP>                                                                     \
+   : trunc ? kernel<__VA_ARGS__ true, false, LOGP>                                                                    \
+           : kernel<__VA_ARGS__ false, false, LOGP>)
+#define T2H_TAIL_KERNEL_LOGP(kernel, logp, ...) \
+  ((logp) ? T2H_TAIL_KERNEL_L(kernel, true, __VA_ARGS__) : T2H_TAIL_KERNEL_L(kernel, false, __VA_ARGS__))
 
 template <bool PER_SAMPLE>
 static int trunc_threshold_launch(const float* logits, int32_t n_rows, int32_t n_class, int32_t top_k, uint32_t top_p_q,
@@ -1192,6 +1276,16 @@ extern "C" int t2h_confidence_commit_per_sample(const t2h_confidence_commit_args
   return confidence_commit_launch<true>(args, stream);
 }
 
+extern "C" int t2h_logp_summary(const float* logp, int32_t B, int32_t T, float* sum, int32_t* count, float* min,
+                                void* stream) {
+  T2H_REQUIRE(logp && sum && count && min, "t2h_logp_summary: NULL pointer");
+  T2H_REQUIRE(B > 0 && T > 0, "t2h_logp_summary: bad arguments (B=%d T=%d)", B, T);
+  hipLaunchKernelGGL(logp_summary_kernel, dim3(B), dim3(LS_THREADS), 0, static_cast<hipStream_t>(stream), logp, T, sum,
+                     count, min);
+  T2H_CHECK_LAUNCH("t2h_logp_summary");
+  return T2H_OK;
+}
+
 extern "C" int t2h_embed_sum4_f32(const int64_t* idx, const int64_t* segm, const int64_t* tex,
                                   const float* tok_emb, const float* pos_emb, const float* segm_emb,
                                   const float* tex_emb, float* x, int32_t B, int32_t T, int32_t C,
@@ -1264,12 +1358,12 @@ static int sample_heads_launch(const t2h_sample_heads_args* args, const t2h_samp
     const dim3 lgrid(a.n_rows * SL_SPLIT), pgrid(a.n_rows);
     hipLaunchKernelGGL((params ? sample_logits_kernel<512, true> : sample_logits_kernel<512, false>), lgrid,
                        dim3(SL_THREADS), 0, s, a, a.logits_ws, params, T);
-    hipLaunchKernelGGL(T2H_TAIL_KERNEL(sample_pick_kernel, ), pgrid, dim3(SH_THREADS), 0, s, a, a.logits_ws, params, T);
+    hipLaunchKernelGGL(T2H_TAIL_KERNEL_LOGP(sample_pick_kernel, a.logp, ), pgrid, dim3(SH_THREADS), 0, s, a, a.logits_ws, params, T);
     T2H_CHECK_LAUNCH("t2h_sample_heads");
     return T2H_OK;
   }
   const size_t lds = (size_t)(a.n_class + 2 * (SH_THREADS / 64)) * sizeof(float);
-  hipLaunchKernelGGL(T2H_TAIL_KERNEL(sample_heads_kernel, 512, ), dim3(a.n_rows), dim3(SH_THREADS), lds, s, a, params, T);
+  hipLaunchKernelGGL(T2H_TAIL_KERNEL_LOGP(sample_heads_kernel, a.logp, 512, ), dim3(a.n_rows), dim3(SH_THREADS), lds, s, a, params, T);
   T2H_CHECK_LAUNCH("t2h_sample_heads");
   return T2H_OK;
 }

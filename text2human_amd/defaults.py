@@ -147,6 +147,18 @@ def with_truncation(opt, top_k=None, top_p=None):
     return opt
 
 
+def with_best_of(opt, n=1):
+    """`opt` with the key that makes sample_and_refine / inference draw n candidates per batch and keep, per image, the
+    one with the highest mean log-probability per drawn token (options.sampling_best_of; 1 or None: off, the key is
+    removed).  Returns opt."""
+    from . import options
+    if n is None or options.best_of_value(n) == 1:
+        opt.pop('sample_best_of', None)
+    else:
+        opt['sample_best_of'] = int(n)
+    return opt
+
+
 def with_refine_sampling(opt, temp=None, top_k=None, top_p=None):
     """`opt` with the keys that make sample_and_refine / inference DRAW the bottom (detail) indices from the
     index-prediction heads' softmax instead of taking its mode (options.refine_sampling; all None: off).  Returns opt."""

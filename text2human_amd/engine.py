@@ -721,16 +721,20 @@ def _initial_state(init, tex_tok, n_books, mask_id, n_class, x_t=None, out=None)
     return x_t.fill_(mask_id), out.fill_(-1), None
 
 
-def _round(net, x_t, out, segm_tok, tex_tok, rows, n_rows, noise, temp, logits_ws, trunc_kw, defer=True, active=None):
+def _round(net, x_t, out, segm_tok, tex_tok, rows, n_rows, noise, temp, logits_ws, trunc_kw, defer=True, active=None,
+           logp=None):
     """One round of the reference's loop: the transformer on x_t (defer: the last layer's tail on the listed rows only,
     and only the first `active` samples), then the tokens of the first n_rows of `rows` drawn into x_t / out.  temp /
-    trunc_kw: the scalar controls (_trunc_kw), or temp None and the per-image table (_per_image_kw)."""
+    trunc_kw: the scalar controls (_trunc_kw), or temp None and the per-image table (_per_image_kw).  logp (f32 [B*T],
+    None = off): the drawn rows' log-probabilities (ops.sample_heads)."""
     compact = False
     if defer:
         net.hidden(x_t, segm_tok, tex_tok, defer_tail=True, active=active)
         hidden, compact = net.finish_tail(rows, n_rows)
     else:
         hidden = net.hidden(x_t, segm_tok, tex_tok)
+    if logp is not None:  # (without it: today's call, keyword for keyword)
+        trunc_kw = dict(trunc_kw, logp=logp)
     ops.sample_heads(hidden, *net.final_norm_and_heads(), {}, rows, n_rows, tex_tok.view(-1), temp, x_t, out,
                      row_noise=noise, hidden_compact=compact, logits_ws=logits_ws, **trunc_kw)
 
@@ -744,7 +748,8 @@ class RoundGraph:
     round -- a power of two --, temperature) for every count of running samples, before the first run
     (prepare), replayed for every round of every run."""
 
-    def __init__(self, net, B, T, steps, maxr, n_books, n_class, temp, mask_id, dev, trunc=(0, 0), per_image=False):
+    def __init__(self, net, B, T, steps, maxr, n_books, n_class, temp, mask_id, dev, trunc=(0, 0), per_image=False,
+                 logp=False):
         i64 = lambda *s: torch.empty(s, dtype=torch.int64, device=dev)
         i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)
         # (a weak reference: net._graphs owns this object -- a strong one would make a cycle that only the cyclic
@@ -764,6 +769,9 @@ class RoundGraph:
         self.cur_rows, self.cur_offs, self.cur_rng = i32(maxr), i64(maxr), i32(maxr)
         self.round_ctr, self.seed = i32(1), i64(1)
         self.logits_ws = torch.empty((maxr, n_class), dtype=torch.float32, device=dev)
+        # per-token log-probabilities (return_logp): a persistent buffer the captured tail points to, NaN-filled by run()
+        # beside the initial state; None = the tail without them (part of the graph key)
+        self.logp = torch.empty(B * T, dtype=torch.float32, device=dev) if logp else None
         self.stream = torch.cuda.Stream(device=dev)
         self.B = B
         self.graphs = {}  # samples still running (a prefix of the batch, schedule.leave_order) -> captured round
@@ -789,7 +797,8 @@ class RoundGraph:
         ops.schedule_advance(self.rows_tbl, self.offs_tbl, self.rng_tbl, self.round_ctr, self.cur_rows, self.cur_offs,
                              self.cur_rng, self.maxr)
         _round(self._net(), self.x_t, self.out, self.segm, self.tex, self.cur_rows, self.maxr,
-               ('philox', self.seed, self.cur_offs, self.cur_rng), self.temp, self.logits_ws, self.trunc, active=k)
+               ('philox', self.seed, self.cur_offs, self.cur_rng), self.temp, self.logits_ws, self.trunc, active=k,
+               logp=self.logp)
 
     def capture(self, k):
         g = torch.cuda.CUDAGraph()
@@ -831,6 +840,8 @@ class RoundGraph:
             self.segm.copy_(segm_tok)
             self.tex.copy_(tex_tok)
             _initial_state(init, self.tex, self.out.shape[0], self.mask_id, self.n_class, self.x_t, self.out)
+            if self.logp is not None:
+                self.logp.fill_(float('nan'))  # (a row that is never drawn keeps it)
             self.round_ctr.zero_()
             self.seed.fill_(schedule.as_int64(sched.seed))  # (a uint64 seed >= 2^63 in its two's-complement form)
             for r in range(R):
@@ -853,19 +864,24 @@ def _per_image_kw(params, T):
     return dict(params=params, rows_per_sample=int(T))
 
 
-def round_graph_key_per_image(B, T, sample_steps, maxr, mask_id, n_books, x8):
+def round_graph_key_per_image(B, T, sample_steps, maxr, mask_id, n_books, x8, logp=False):
     """The key of the captured rounds of per-image runs: the table is read from a buffer of the graph, so neither
-    temperatures nor truncation settings are held by value -- runs with different values share the captures."""
-    return (B, T, sample_steps, maxr, int(mask_id), n_books, bool(x8), 'per-sample')
+    temperatures nor truncation settings are held by value -- runs with different values share the captures.  logp
+    (the tail that also writes log-probabilities): one more trailing element, absent without it."""
+    return (B, T, sample_steps, maxr, int(mask_id), n_books, bool(x8), 'per-sample') + (('logp', ) if logp else ())
 
 
-def round_graph_key(B, T, sample_steps, maxr, temp, mask_id, n_books, x8, trunc=(0, 0)):
-    """What a captured round (RoundGraph) holds BY VALUE: two calls share a graph iff this key is equal."""
-    return (B, T, sample_steps, maxr, float(temp), int(mask_id), n_books, bool(x8), int(trunc[0]), int(trunc[1]))
+def round_graph_key(B, T, sample_steps, maxr, temp, mask_id, n_books, x8, trunc=(0, 0), logp=False):
+    """What a captured round (RoundGraph) holds BY VALUE: two calls share a graph iff this key is equal.  logp (the tail
+    that also writes log-probabilities): one more trailing element, absent without it -- the keys, and so the captures,
+    of runs without it are what they always were."""
+    return ((B, T, sample_steps, maxr, float(temp), int(mask_id), n_books, bool(x8), int(trunc[0]), int(trunc[1])) +
+            (('logp', ) if logp else ()))
 
 
 def sample_tokens(net, segm_tok, tex_tok, sample_steps, mask_id, temp=1.0, noise=None,
-                  n_books=18, step_hook=None, round_hook=None, compact=None, init=None, top_k=None, top_p=None):
+                  n_books=18, step_hook=None, round_hook=None, compact=None, init=None, top_k=None, top_p=None,
+                  return_logp=False):
     """BaseSampleModel.sample_fn (models/sample_model.py:256-328) on device.
 
     The unmasking schedule and every generator offset are computed up front (build_schedule: they
@@ -891,6 +907,11 @@ def sample_tokens(net, segm_tok, tex_tok, sample_steps, mask_id, temp=1.0, noise
     rows with keep != 0 start as their source token and are never resampled; everything else is the loop above, with
     the generator consumed exactly as the reference's loop started from that state would consume it.
 
+    return_logp: returns (out, logp) -- logp float32 [B*T] in the caller's sample order, the natural-log probability of
+    every drawn token under the full softmax of logits / temp at the moment it was drawn (truncation
+    changes the token, never the distribution); NaN for rows that were never drawn (kept by a region edit).  Tokens and
+    generator are those of the call without it.
+
     Test hooks, called after each round and allowed to overwrite x_t in place (teacher forcing):
     round_hook(r, steps, x_t, out) with steps[b] = the step sample b just took (0 = idle);
     step_hook(t, x_t, out) (compact=False only; steps that change no token are skipped)."""
@@ -910,7 +931,7 @@ def sample_tokens(net, segm_tok, tex_tok, sample_steps, mask_id, temp=1.0, noise
     # whole batch each round, and the counts say so)
     net.last_stats = schedule.stats(sched.round_steps, sample_steps, sched.active if defer else None, kept=sched.kept)
     tex_tok = tex_flat.view(B, T)
-    in_batch_order = lambda out: out  # [n_books, n] in the schedule's sample order -> the caller's
+    in_batch_order = lambda out: out  # [..., n] in the schedule's sample order -> the caller's
     if sched.perm is not None:
         perm_t = torch.from_numpy(sched.perm).to(dev)
         segm_tok, tex_tok = segm_tok[perm_t].contiguous(), tex_tok[perm_t].contiguous()
@@ -919,7 +940,7 @@ def sample_tokens(net, segm_tok, tex_tok, sample_steps, mask_id, temp=1.0, noise
         if table is not None:  # the kernels index the table by the sample's position in the batch THEY see
             table = table[sched.perm]
         caller_rows = torch.from_numpy(schedule.in_caller_order(sched.perm, B, T)).to(dev)
-        in_batch_order = lambda out: out[:, caller_rows]
+        in_batch_order = lambda out: out[..., caller_rows]
 
     # Default (T2H_GRAPH=0 opts out): every round is ONE replay of a captured launch sequence (RoundGraph)
     # instead of ~180 launches from this thread.  The GPU work is the same; what changes is the host side --
@@ -934,32 +955,35 @@ def sample_tokens(net, segm_tok, tex_tok, sample_steps, mask_id, temp=1.0, noise
         maxr = min(net.TRIM_MAX_ROWS, max(16, 1 << (int(sched.max_rows) - 1).bit_length()))
         net._buffers(n, net.desc['C'], dev)  # (a change of batch size drops the graphs of the old buffers)
         if table is None:
-            key = round_graph_key(B, T, sample_steps, maxr, temp, mask_id, n_books, net.x8, sp.trunc)
+            key = round_graph_key(B, T, sample_steps, maxr, temp, mask_id, n_books, net.x8, sp.trunc, logp=return_logp)
         else:
-            key = round_graph_key_per_image(B, T, sample_steps, maxr, mask_id, n_books, net.x8)
+            key = round_graph_key_per_image(B, T, sample_steps, maxr, mask_id, n_books, net.x8, logp=return_logp)
         if key not in net._graphs:
             net._graphs[key] = RoundGraph(net, B, T, sample_steps, maxr, n_books, n_class, temp, mask_id, dev,
-                                          trunc=sp.trunc, per_image=table is not None)
-        return in_batch_order(net._graphs[key].run(sched, segm_tok, tex_tok, init=init, params=table).clone())
+                                          trunc=sp.trunc, per_image=table is not None, logp=return_logp)
+        graph = net._graphs[key]
+        out = in_batch_order(graph.run(sched, segm_tok, tex_tok, init=init, params=table).clone())
+        return (out, in_batch_order(graph.logp.clone())) if return_logp else out
     tail_kw = _trunc_kw(sp.trunc) if table is None else _per_image_kw(ops.sample_params_tensor(table, dev), T)
     x_t, out, _ = _initial_state(init, tex_tok, n_books, mask_id, n_class)
+    logp = torch.full((n, ), float('nan'), dtype=torch.float32, device=dev) if return_logp else None
     logits_ws = torch.empty((max(sched.max_rows, 1), n_class), dtype=torch.float32, device=dev)
     for r in range(sched.n_rounds):
         lo, hi = int(sched.start[r]), int(sched.start[r + 1])
         k = int(sched.active[r]) if sched.active is not None else None
         _round(net, x_t, out, segm_tok, tex_tok, sched.rows[lo:hi], hi - lo, sched.row_noise(lo, hi), sp.temp, logits_ws,
-               tail_kw, defer, k)
+               tail_kw, defer, k, logp)
         if round_hook is not None:
             round_hook(r, sched.round_steps[r], x_t, out)
         if step_hook is not None:
             step_hook(int(sched.round_steps[r].max()), x_t, out)
     if net.split:
         check_split_overflow('index sampler')
-    return in_batch_order(out)
+    return (in_batch_order(out), in_batch_order(logp)) if return_logp else in_batch_order(out)
 
 
 def sample_tokens_confidence(net, segm_tok, tex_tok, mask_id, rounds=16, temp=1.0, choice_temp=4.5, noise=None,
-                             n_books=18, round_hook=None, init=None, top_k=None, top_p=None):
+                             n_books=18, round_hook=None, init=None, top_k=None, top_p=None, return_logp=False):
     """Confidence-ordered parallel decoding ("Confidence-ordered decoding"; opt-in, sample_tokens is the
     reference's loop): `rounds` rounds, each ONE transformer evaluation of the whole batch, a token + confidence for
     every still-masked row (t2h_confidence_tail) and, per sample, the commit of the k_r rows with the largest score
@@ -973,6 +997,8 @@ def sample_tokens_confidence(net, segm_tok, tex_tok, mask_id, rounds=16, temp=1.
     the token a row draws, never its confidence (the log-probability under the full softmax).  round_hook(r, x_t, out, tokens, conf, scores) is called after round
     r = 1 .. R and may overwrite x_t / out in place (teacher forcing); rounds after the last masked row of the whole
     batch are not evaluated (their draws are still counted).  Returns int64 [n_books, B*T] (-1 off-texture).
+    return_logp: returns (out, logp), logp float32 [B*T] = the confidence (a log-probability already) of every committed
+    row as the round that committed it formed it, NaN for rows that were never committed (kept by a region edit).
 
     rounds / choice_temp / temp / top_k / top_p may each be a sequence with one entry per image ("Per-image
     sampling controls"): the run has R = max rounds rounds and consumes the generator as the scalar call with R rounds;
@@ -1044,6 +1070,9 @@ def sample_tokens_confidence(net, segm_tok, tex_tok, mask_id, rounds=16, temp=1.
     tok = torch.empty(n, dtype=torch.int32, device=dev)
     conf = torch.empty(n, dtype=torch.float32, device=dev)
     scores = torch.empty(n, dtype=torch.float32, device=dev)
+    commit_kw = {}
+    if return_logp:
+        commit_kw['logp'] = logp = torch.full((n, ), float('nan'), dtype=torch.float32, device=dev)
     group_ws = ops.confidence_group_ws(n, n_books, dev)
     logits_ws = torch.empty((n, n_class), dtype=torch.float32, device=dev)
     lnf_g, lnf_b, heads = net.final_norm_and_heads()
@@ -1058,7 +1087,7 @@ def sample_tokens_confidence(net, segm_tok, tex_tok, mask_id, rounds=16, temp=1.
         ops.confidence_tail(hidden, lnf_g, lnf_b, heads, tex_flat, x_t.view(-1), mask_id, sp.temp, noise_e, tok, conf,
                             group_ws=group_ws, logits_ws=logits_ws, **trunc_kw)
         ops.confidence_commit(conf, tok, tex_flat, noise_u, cur_k, cur_tau.view(torch.float32), mask_id, x_t, out,
-                              n_class, scores=scores, per_sample=per_image)
+                              n_class, scores=scores, per_sample=per_image, **commit_kw)
         if round_hook is not None:
             round_hook(r, x_t, out, tok, conf, scores)
     if not philox:  # the draws of the rounds that were not evaluated
@@ -1067,7 +1096,7 @@ def sample_tokens_confidence(net, segm_tok, tex_tok, mask_id, rounds=16, temp=1.
             noise.uniform(r, (n, ))
     if net.split:
         check_split_overflow('index sampler')
-    return out
+    return (out, logp) if return_logp else out
 
 
 # ---------------------------------------------------------------- UNet + heads

@@ -113,20 +113,24 @@ class BaseSampleModel():
 
     # ------------------------------------------------------------ stage S
     @torch.no_grad()
-    def sample_fn(self, temp=1.0, sample_steps=None, top_k=None, top_p=None):
+    def sample_fn(self, temp=1.0, sample_steps=None, top_k=None, top_p=None, return_logp=False):
         """models/sample_model.py:256-328 -> list of 18 int64 [B, 512].  top_k / top_p (not in the reference; DESIGN.md
         "Truncated sampling"): every draw only among the k most likely classes / the smallest set of most likely classes
         holding top_p of the probability.  None = off = the reference's draw.  temp / top_k / top_p may each be a
         sequence with one entry per image of the batch (DESIGN.md "Per-image sampling controls"): image b is then the
-        image b of the call with its own values as scalars."""
-        return self._sample(temp, sample_steps or self.sample_steps, top_k=top_k, top_p=top_p)
+        image b of the call with its own values as scalars.  return_logp: -> (lists, logp), logp float32 [B, 512] = the
+        log-probability of every drawn token under the full softmax of logits / temp when it was drawn (DESIGN.md 4.6f;
+        NaN: never drawn); tokens and generator are those of the call without it."""
+        return self._sample(temp, sample_steps or self.sample_steps, top_k=top_k, top_p=top_p, return_logp=return_logp)
 
     @torch.no_grad()
-    def sample_fn_confidence(self, rounds=16, temp=1.0, choice_temp=4.5, top_k=None, top_p=None):
+    def sample_fn_confidence(self, rounds=16, temp=1.0, choice_temp=4.5, top_k=None, top_p=None, return_logp=False):
         """Confidence-ordered parallel decoding (opt-in; DESIGN.md "Confidence-ordered decoding"): all tokens in
         `rounds` transformer evaluations instead of one per active step -> list of 18 int64 [B, 512] like sample_fn.
-        rounds / choice_temp / temp / top_k / top_p may each be a sequence with one entry per image."""
-        return self._sample(temp, None, confidence=self._confidence_args(rounds, choice_temp), top_k=top_k, top_p=top_p)
+        rounds / choice_temp / temp / top_k / top_p may each be a sequence with one entry per image.  return_logp: as in
+        sample_fn (the confidence of every committed token, from the round that committed it)."""
+        return self._sample(temp, None, confidence=self._confidence_args(rounds, choice_temp), top_k=top_k, top_p=top_p,
+                            return_logp=return_logp)
 
     @staticmethod
     def _confidence_args(rounds, choice_temp):
@@ -142,10 +146,12 @@ class BaseSampleModel():
         """(top_k, top_p) of the options `sample_top_k` / `sample_top_p` (None, None: off)."""
         return options.sampling_truncation(self.opt)
 
-    def _sample(self, temp, sample_steps, init=None, confidence=None, top_k=None, top_p=None):
+    def _sample(self, temp, sample_steps, init=None, confidence=None, top_k=None, top_p=None, return_logp=False):
         """sample_fn's body (init: engine.sample_tokens' initial state of a region edit; confidence = (rounds,
         choice_temp): engine.sample_tokens_confidence instead of the reference's loop; top_k / top_p: truncated
-        sampling, passed to every attempt of the fall-back chain below)."""
+        sampling, passed to every attempt of the fall-back chain below; return_logp: -> (lists, logp [B, 512]), the
+        log-probabilities of the attempt that produced the tokens)."""
+        logp_kw = dict(return_logp=True) if return_logp else {}  # (without it: today's calls, keyword for keyword)
         ops.sampling_params(self.batch_size, temp, top_k, top_p)  # (raises before anything is evaluated or drawn)
         tex_tok = self._texture_tokens(self.texture_mask)
         # The reference computes ANY checkpoint in fp32 (transformer_arch.py:91-99).  The split-precision kernels
@@ -163,11 +169,11 @@ class BaseSampleModel():
                         out = engine.sample_tokens_confidence(net, self.segm_tokens.contiguous(), tex_tok, self.mask_id,
                                                               rounds=confidence[0], temp=temp,
                                                               choice_temp=confidence[1], noise=self.noise, init=init,
-                                                              top_k=top_k, top_p=top_p)
+                                                              top_k=top_k, top_p=top_p, **logp_kw)
                     else:
                         out = engine.sample_tokens(net, self.segm_tokens.contiguous(), tex_tok, sample_steps,
                                                    self.mask_id, temp=temp, noise=self.noise, init=init,
-                                                   top_k=top_k, top_p=top_p)
+                                                   top_k=top_k, top_p=top_p, **logp_kw)
                     break
                 except engine.X8RangeError as e:
                     # an activation beyond 14x its calibration maximum: the 8-bit planes saturated, the fp16 planes are
@@ -185,7 +191,49 @@ class BaseSampleModel():
         finally:
             self.sampler_fn.x8 = x8_was
         b = self.batch_size
+        if return_logp:
+            out, logp = out
+            return [out[i].view(b, -1) for i in range(out.shape[0])], logp.view(b, -1)
         return [out[i].view(b, -1) for i in range(out.shape[0])]
+
+    @torch.no_grad()
+    def sample_best_of(self, n, order=None, **sampling_kwargs):
+        """Best-of-N by likelihood (opt-in): runs the selected sampler n times in a row on the fed batch
+        -- candidate c is, bit for bit, the c-th consecutive plain call from the same generator state, and the generator
+        ends where n calls leave it -- and keeps, per image, the candidate with the highest mean log-probability per
+        drawn token (t2h_logp_summary: sum / count; no drawn token: -inf; ties go to the earlier candidate).
+        order: 'random' (sample_fn), 'confidence' (sample_fn_confidence) or None = what the options select;
+        sampling_kwargs go to that method unchanged (per-image controls included).  -> (lists, logp, score, choice):
+        18 x int64 [B, 512] and float32 [B, 512] of the kept candidates, score float32 [B], choice int64 [B].  n = 1 is
+        the plain call.  The selection runs on the device; nothing is read back."""
+        n = options.best_of_value(n)
+        if order is None:
+            order = 'confidence' if self._confidence_options() is not None else 'random'
+            if order == 'confidence' and 'rounds' not in sampling_kwargs and 'choice_temp' not in sampling_kwargs:
+                sampling_kwargs = dict(sampling_kwargs)
+                sampling_kwargs['rounds'], sampling_kwargs['choice_temp'] = self._confidence_options()
+        if order not in options.SAMPLE_ORDERS:
+            raise ValueError(f'order must be one of {options.SAMPLE_ORDERS}, got {order!r}')
+        sampler = self.sample_fn_confidence if order == 'confidence' else self.sample_fn
+        b, t_len = self.batch_size, self.shape[0] * self.shape[1]
+        best = best_logp = best_score = choice = None
+        for c in range(n):
+            lists, logp = sampler(return_logp=True, **sampling_kwargs)
+            logp = logp.contiguous()
+            s, cnt, _ = ops.logp_summary(logp)
+            score = torch.where(cnt > 0, s / cnt.to(torch.float32), torch.full_like(s, float('-inf')))
+            cand = torch.stack([x.reshape(-1) for x in lists]).contiguous()  # [18, B*512]
+            if c == 0:
+                best, best_logp, best_score = cand, logp, score
+                choice = torch.zeros(b, dtype=torch.int64, device=self.device)
+                continue
+            better = score > best_score  # (strictly: a tie keeps the earlier candidate)
+            rows = better.to(torch.uint8).repeat_interleave(t_len).contiguous()
+            ops.merge_kept_indices(cand, rows, best)  # best[:, r] = cand[:, r] for the rows of the images that improved
+            best_logp = torch.where(better[:, None], logp, best_logp)
+            best_score = torch.where(better, score, best_score)
+            choice = torch.where(better, torch.full_like(choice, c), choice)
+        return [best[i].view(b, -1) for i in range(best.shape[0])], best_logp, best_score, choice
 
     # ------------------------------------------------------------ region editing
     # DESIGN.md "Editing a region": the reference loop started from a partially known state.  A token row is kept
@@ -227,14 +275,15 @@ class BaseSampleModel():
 
     @torch.no_grad()
     def resample_fn(self, top_indices_list, keep, temp=1.0, sample_steps=None, order='random', rounds=None,
-                    choice_temp=4.5, top_k=None, top_p=None):
+                    choice_temp=4.5, top_k=None, top_p=None, return_logp=False):
         """sample_fn started from `top_indices_list` (18 x int64 [B, 512], e.g. an earlier sample_fn result or a photo's
         top_encode indices) with the rows where keep [B, 512] is nonzero kept.  -> list of 18 int64 [B, 512] in
         sample_fn's format.  A kept row must have an index under the CURRENT texture map (T2HError otherwise; nothing
         changes).  order='confidence': the masked rows are filled by confidence-ordered decoding in `rounds` (default
         16) rounds, every sample on the schedule of its own number of resampled rows.  top_k / top_p: truncated
         sampling of the resampled rows, as in sample_fn.  temp / top_k / top_p / rounds / choice_temp may each be a
-        sequence with one entry per image, as in sample_fn / sample_fn_confidence."""
+        sequence with one entry per image, as in sample_fn / sample_fn_confidence.  return_logp: -> (lists, logp) as in
+        sample_fn; the kept rows are NaN."""
         if order not in ('random', 'confidence'):
             raise ValueError(f"order must be 'random' or 'confidence', got {order!r}")
         init = (self._token_lists(top_indices_list, 'resample_fn'), self._keep_rows(keep))
@@ -242,7 +291,7 @@ class BaseSampleModel():
             rounds = int(rounds or 16)
         confidence = self._confidence_args(rounds, choice_temp) if order == 'confidence' else None
         return self._sample(temp, sample_steps or self.sample_steps, init=init, confidence=confidence, top_k=top_k,
-                            top_p=top_p)
+                            top_p=top_p, return_logp=return_logp)
 
     @torch.no_grad()
     def edit_and_refine(self, top_indices_list, region=None, labels=None, bot_indices_list=None, save_dir=None,
@@ -459,7 +508,18 @@ class BaseSampleModel():
         top_k, top_p = self._truncation_options()  # (options: sample_top_k / sample_top_p)
         trunc = {k: v for k, v in (('top_k', top_k), ('top_p', top_p)) if v is not None}
         refine_kw = self._refine_options()  # (options: refine_temp / refine_top_k / refine_top_p)
-        if confidence is not None:  # (options: sample_order: confidence)
+        best_of = options.sampling_best_of(self.opt)  # (options: sample_best_of; 1: the calls below, as always)
+        if best_of > 1:
+            kw = dict(trunc, temp=1)
+            if confidence is not None:
+                kw.update(rounds=confidence[0], choice_temp=confidence[1])
+            else:
+                kw.update(sample_steps=self.sample_steps)
+            sampled_top_indices_list, _, score, choice = self.sample_best_of(
+                best_of, order='confidence' if confidence is not None else 'random', **kw)
+            for i, (c, s) in enumerate(zip(choice.tolist(), score.tolist())):
+                logger.info(f'best of {best_of}: image {i} keeps candidate {c} (mean log-probability per token {s:.4f})')
+        elif confidence is not None:  # (options: sample_order: confidence)
             sampled_top_indices_list = self.sample_fn_confidence(rounds=confidence[0], temp=1, choice_temp=confidence[1],
                                                                  **trunc)
         elif trunc:

@@ -962,7 +962,7 @@ def _philox_fields(a, numel, device, **fields):
 
 def sample_heads(hidden, lnf_g, lnf_b, w_heads, expo_by_head, rows, n_rows, tex, temp, x_t, out_idx, split=True,
                  philox=None, hidden_compact=False, row_noise=None, logits_ws=None, top_k=0, top_p=1.0, params=None,
-                 rows_per_sample=None):
+                 rows_per_sample=None, logp=None):
     """All heads in one launch: `rows` (int32, first n_rows valid) are the changed token
     rows, expo_by_head {head: [n, n_class] Exp(1) draw}, w_heads [n_heads, n_class, C],
     out_idx [n_heads, n].  philox = (seed, {head: generator offset}): the noise of the listed heads is
@@ -973,8 +973,13 @@ def sample_heads(hidden, lnf_g, lnf_b, w_heads, expo_by_head, rows, n_rows, tex,
     ('explicit', expo_rows f32 [*, n_class], slots int32 [>= n_rows]) = per-listed-row explicit draws.
     top_k / top_p: truncated sampling (truncation_settings; the defaults are off = the kernels without it).
     params (sample_params_tensor) + rows_per_sample: per-image controls (t2h_sample_heads_per_sample) -- row r is drawn
-    with params[r // rows_per_sample]; temp / top_k / top_p are then not read."""
+    with params[r // rows_per_sample]; temp / top_k / top_p are then not read.
+    logp (f32, >= n elements, indexed by token row like x_t; None = off, the kernels without it): every listed row
+    also gets the log-probability of its token under the full softmax of logits / temp."""
     _chk_f32(hidden, lnf_g, lnf_b, w_heads, *expo_by_head.values())
+    if logp is not None:
+        _chk_f32(logp)
+        assert logp.is_contiguous() and logp.numel() >= out_idx.shape[1], (tuple(logp.shape), tuple(out_idx.shape))
     trunc = truncation_settings(top_k, top_p, w_heads.shape[1]) if params is None else (0, 0)
     if int(n_rows) == 0:
         return
@@ -993,6 +998,8 @@ def sample_heads(hidden, lnf_g, lnf_b, w_heads, expo_by_head, rows, n_rows, tex,
     a.temp, a.n_rows, a.n, a.C, a.n_class, a.n_heads = (float(temp) if params is None else 1.0), int(n_rows), n, C, n_class, n_heads
     a.hidden_compact = int(bool(hidden_compact))
     a.top_k, a.top_p_q = trunc
+    if logp is not None:
+        a.logp = logp.data_ptr()
     if (split or philox is not None or hidden_compact or row_noise is not None) and n_rows > 0:
         # logits scratch: 8 workgroups per row share the weight stream
         ws = logits_ws if logits_ws is not None else torch.empty((int(n_rows), n_class), device=hidden.device,
@@ -1073,11 +1080,13 @@ def confidence_tail(hidden, lnf_g, lnf_b, w_heads, tex, x_t, mask_id, temp, nois
     return tok, conf
 
 
-def confidence_commit(conf, tok, tex, noise, k, tau, mask_id, x_t, out, n_class, scores=None, per_sample=False):
+def confidence_commit(conf, tok, tex, noise, k, tau, mask_id, x_t, out, n_class, scores=None, per_sample=False,
+                      logp=None):
     """Commits, per sample, the k[b] masked rows with the largest score conf + tau * gumbel(U) (t2h_confidence_commit):
     x_t int64 [B, T] and out int64 [n_heads, B * T] are updated in place.  k int32 [>= B] and tau f32 [>= 1] are device
     tensors; noise: ('explicit', U f32 [B * T]) or ('philox', seed, offset) = the elements of torch's `rand(B * T)`.
-    per_sample: tau is f32 [>= B], sample b scores with tau[b] (t2h_confidence_commit_per_sample)."""
+    per_sample: tau is f32 [>= B], sample b scores with tau[b] (t2h_confidence_commit_per_sample).
+    logp (f32, >= B * T elements; None = off): a committed row gets logp[row] = conf[row], other rows are not written."""
     _chk_f32(conf, tau)
     _chk_i64(tex, x_t, out)
     B, T = x_t.shape
@@ -1101,10 +1110,29 @@ def confidence_commit(conf, tok, tex, noise, k, tau, mask_id, x_t, out, n_class,
         assert scores.numel() == n
         a.scores = scores.data_ptr()
     a.B, a.T, a.n_heads, a.n_class = B, T, n_heads, int(n_class)
+    if logp is not None:
+        _chk_f32(logp)
+        assert logp.is_contiguous() and logp.numel() >= n
+        a.logp = logp.data_ptr()
     if per_sample:
         return check(_lib.load().t2h_confidence_commit_per_sample(ctypes.byref(a), _stream()),
                      't2h_confidence_commit_per_sample')
     check(_lib.load().t2h_confidence_commit(ctypes.byref(a), _stream()), 't2h_confidence_commit')
+
+
+def logp_summary(logp, B=None, T=None):
+    """Per-image summary of per-token log-probabilities (t2h_logp_summary): logp f32 [B, T] (or flat with B, T given),
+    NaN = never drawn -> (sum f32 [B], count int32 [B], min f32 [B]); an image's numbers do not depend on its place in
+    the batch.  An image without a drawn row: (0, 0, +inf)."""
+    _chk_f32(logp)
+    if B is None:
+        B, T = logp.shape
+    assert logp.is_contiguous() and logp.numel() == int(B) * int(T)
+    dev = logp.device
+    s, m = torch.empty(int(B), dtype=torch.float32, device=dev), torch.empty(int(B), dtype=torch.float32, device=dev)
+    c = torch.empty(int(B), dtype=torch.int32, device=dev)
+    check(_lib.load().t2h_logp_summary(_p(logp), int(B), int(T), _p(s), _p(c), _p(m), _stream()), 't2h_logp_summary')
+    return s, c, m
 
 
 def sample_head(hidden, lnf_g, lnf_b, w_head, expo, changes, tex, head, temp, x_t, out_idx):

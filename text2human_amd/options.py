@@ -156,6 +156,22 @@ def sampling_truncation(opt):
     return top_k, top_p
 
 
+# Best-of-N selection by per-token log-probability.  Absent key, or 1 = off = one plain call.
+def best_of_value(n):
+    """the validated candidate count of sample_best_of: an integer >= 1 (ValueError naming the value otherwise --
+    callers check before anything is drawn)"""
+    import numbers
+    if isinstance(n, bool) or not isinstance(n, numbers.Integral) or int(n) < 1:
+        raise ValueError(f'sample_best_of must be an integer >= 1 (1: off), got {n!r}')
+    return int(n)
+
+
+def sampling_best_of(opt):
+    """-> the candidate count of the option `sample_best_of` (1 where absent: the existing path), validated."""
+    n = opt.get('sample_best_of')
+    return 1 if n is None else best_of_value(n)
+
+
 # Sampled bottom-index refinement (DESIGN.md 4.6e).  Absent keys = off = the argmax of the index-prediction heads.
 REFINE_KEYS = ('refine_temp', 'refine_top_k', 'refine_top_p')
 

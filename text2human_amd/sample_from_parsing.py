@@ -105,6 +105,9 @@ def cli_parser():
     ap.add_argument('--top-p', type=float, default=None,
                     help='index sampler: draw every token from the most likely classes that hold this share of the '
                          'probability (overrides sample_top_p)')
+    ap.add_argument('--best-of', type=int, default=None,
+                    help='index sampler: draw N candidates per batch and keep, per image, the one with the highest mean '
+                         'log-probability per drawn token (overrides sample_best_of; 1: off)')
     ap.add_argument('--refine-temp', type=float, default=None,
                     help='refinement: draw the bottom (detail) indices from the index-prediction softmax at this '
                          'temperature instead of taking its mode (overrides refine_temp)')
@@ -120,12 +123,13 @@ def apply_cli(opt, args):
     """The command line's overrides of the YAML's sampling keys, validated (a bad value ends the run here, before the
     checkpoints are read).  Returns opt."""
     for key, v in (('sample_order', args.order), ('confidence_rounds', args.rounds), ('sample_top_k', args.top_k),
-                   ('sample_top_p', args.top_p), ('refine_temp', args.refine_temp),
+                   ('sample_top_p', args.top_p), ('sample_best_of', args.best_of), ('refine_temp', args.refine_temp),
                    ('refine_top_k', args.refine_top_k), ('refine_top_p', args.refine_top_p)):
         if v is not None:
             opt[key] = v
     options.sampling_order(opt)
     options.sampling_truncation(opt)
+    options.sampling_best_of(opt)
     options.refine_sampling(opt)
     return opt
 
