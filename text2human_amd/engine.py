@@ -476,7 +476,10 @@ class SamplerNet:
                 mx[i, role] = float(mx_bits[slot_a(i, role)])
                 sa[i, role] = ops.x8_scale_for(mx[i, role])
         if ops.split_overflow(reset=True):
-            raise _lib.T2HError('x8 weight packing overflowed')  # (cannot happen: every scale is derived from its matrix's maximum)
+            # (a guard, not a path: every scale is derived from its matrix's maximum, so |w| s < 256 -- and x8_scale_for
+            # caps it at 2^22, without which the residual plane of a near-zero matrix (max |w| < 3.05e-5: subnormal fp16
+            # plane) left the 8-bit range and this word stayed 0)
+            raise _lib.T2HError('x8 weight packing overflowed')
         self._x8 = {'w': sw, 'a': sa, 'act_max': mx}
 
     def final_norm_and_heads(self):

@@ -461,6 +461,7 @@ def pack_split_rows_host(w):
 
 
 X8_TARGET_MAX = 32.0  # a tensor's calibration maximum is scaled into [16, 32): 14x headroom below e4m3's 448
+X8_SCALE_MIN, X8_SCALE_MAX = 2.0 ** -7, 2.0 ** 22  # the domain of an x8 tensor's scale
 
 
 def x8_scale_for(max_abs, target=X8_TARGET_MAX):
@@ -471,8 +472,18 @@ def x8_scale_for(max_abs, target=X8_TARGET_MAX):
     if not (m > 0.0) or not math.isfinite(m):
         return 1.0
     # (never below 2^-7: 448 / s then stays under fp16's 65504, so a value the 8-bit planes can hold never overflows
-    # the fp16 hi plane first)
-    return max(2.0 ** (math.ceil(math.log2(target / m)) - 1), 2.0 ** -7)
+    # the fp16 hi plane first.  Never above 2^22: where the fp16 hi plane is subnormal the residual l = (x - h) 2048 is
+    # bounded by half a subnormal step, 2^-25 2048 = 2^-14, not by |h| -- l s <= 256 stays inside the 8-bit planes'
+    # 448 for every fp32 x, which the producers' range test |x| s >= 448 alone would not notice)
+    return min(max(2.0 ** (math.ceil(math.log2(target / m)) - 1), X8_SCALE_MIN), X8_SCALE_MAX)
+
+
+def _chk_x8_scale(scale, what):
+    s = float(scale)
+    if not s <= X8_SCALE_MAX:
+        raise ValueError(f'{what}: x8 scale {s:g} is above 2^22: the residual plane of values whose fp16 plane is '
+                         'subnormal would leave the 8-bit range unflagged (ops.x8_scale_for caps the scale there)')
+    return s
 
 
 def absmax_f32(x, out_bits):
@@ -490,11 +501,12 @@ def split_rows_absmax(rows_split, rows, C, out_bits):
 def split_rows_x8(x, scale, out=None):
     """fp32 x [rows, C] -> x8 rows [rows][C/32][hi16 | hi8 | lo8] (same byte size as split rows), 8-bit planes
     scaled by the power of two `scale`."""
+    scale = _chk_x8_scale(scale, 'split_rows_x8')
     _chk_f32(x)
     rows, C = x.shape
     if out is None:
         out = split_rows_empty(rows, C, x.device)
-    check(_lib.load().t2h_split_rows_x8_f32(_p(x), _rows(x), _p(out), rows, C, float(scale), overflow_flag(), _stream()),
+    check(_lib.load().t2h_split_rows_x8_f32(_p(x), _rows(x), _p(out), rows, C, scale, overflow_flag(), _stream()),
           't2h_split_rows_x8_f32')
     return out
 
@@ -511,17 +523,19 @@ def unpack_x8_rows_host(s, rows, C, scale):
 
 def layernorm_x8(x, gamma, beta, out_x8, scale, eps=1e-5):
     """LayerNorm whose result is written in the x8 format."""
+    scale = _chk_x8_scale(scale, 'layernorm_x8')
     _chk_f32(x, gamma, beta)
     assert x.is_contiguous()
     rows, C = x.shape
-    check(_lib.load().t2h_layernorm_x8_f32(_p(x), _p(gamma), _p(beta), _p(out_x8), rows, C, eps, float(scale),
+    check(_lib.load().t2h_layernorm_x8_f32(_p(x), _p(gamma), _p(beta), _p(out_x8), rows, C, eps, scale,
                                            overflow_flag(), _stream()), 't2h_layernorm_x8_f32')
     return out_x8
 
 
 def mha_split_x8(qk_split, ld_cols, vt, B, T, n_head, out_x8, scale):
     """mha_split with the output written in the x8 format."""
-    check(_lib.load().t2h_mha_split_x8_f32(_p(qk_split), ld_cols, _p(vt), _p(out_x8), float(scale), B, T, n_head,
+    scale = _chk_x8_scale(scale, 'mha_split_x8')
+    check(_lib.load().t2h_mha_split_x8_f32(_p(qk_split), ld_cols, _p(vt), _p(out_x8), scale, B, T, n_head,
                                            overflow_flag(), _stream()), 't2h_mha_split_x8_f32')
     return out_x8
 
@@ -541,7 +555,7 @@ def gemm_split(a_split, w_split, M, N, K, out=None, out_split=None, bias=None, r
         g.fmt = 1
         g.lo_mul = 1.0 / (SPLIT_LO_SCALE * float(x8[0]) * float(x8[1]))
     if out_x8_scale is not None:
-        g.out_fmt, g.out_scale = 1, float(out_x8_scale)
+        g.out_fmt, g.out_scale = 1, _chk_x8_scale(out_x8_scale, 'gemm_split(out_x8_scale=)')
     g.ksplit = int(ksplit)  # (> 1: `out` holds ksplit * M rows of partial tiles; experiment, t2h_hip.h)
     g.A, g.B = a_split.data_ptr(), w_split.data_ptr()
     g.C = out.data_ptr() if out is not None else None
