@@ -532,6 +532,26 @@ int t2h_truncation_threshold_per_row(const float* logits, int32_t n_rows, int32_
                                      const t2h_sample_params* params, int32_t rows_per_sample, int32_t scope,
                                      float* theta, int32_t* kept, void* stream);
 
+/* Scoring a given token map: the two-launch form of t2h_sample_heads with the token of every listed row
+ * READ from `targets` instead of drawn.  args->logits_ws and args->logp are required.  Launch 1 is t2h_sample_heads' own
+ * (the same logits, bit for bit, temp from args or from params[row / rows_per_sample]); launch 2, for listed row r with
+ * h = tex[r] and tok = targets[h][r]:
+ *   logp[r] = (l_tok - max l) - logf(se)   (the max, the sum and its order as documented at t2h_sample_heads_args.logp: a
+ *                                           token that t2h_sample_heads drew scores the bits that call wrote)
+ *   x_t[r] = tok + n_class * h, out_idx[h][r] = tok
+ *   rank[r] (optional) = the number of classes j with l_j > l_tok, strictly: 0 = the mode or one of several tied modes.
+ * tok outside [0, n_class) indexes nothing: logp[r] = NaN, rank[r] = -1, x_t / out_idx are left as they were (hosts
+ * validate first: t2h_edit_prefill's check-only form).  No noise is read: expo, the Philox fields, top_k and top_p_q are
+ * ignored -- truncation never changed the distribution logp is taken under.  Rows that are not listed are not written; a
+ * row listed twice is written twice with the same values. */
+typedef struct t2h_score_out {
+  const int64_t* targets;  /* [n_heads][n], the layout of out_idx / src_lists; row r's token is targets[tex[r]][r] */
+  int32_t* rank;           /* optional [n] */
+} t2h_score_out;
+int t2h_score_heads(const t2h_sample_heads_args* args, const t2h_score_out* score, void* stream);
+int t2h_score_heads_per_sample(const t2h_sample_heads_args* args, const t2h_score_out* score,
+                               const t2h_sample_params* params, int32_t rows_per_sample, void* stream);
+
 /* Per-image summary of a run's per-token log-probabilities (logp [B][T] as the sampling tails write it; NaN = the row
  * was never drawn and is skipped): sum[b], count[b] = the number of drawn rows, min[b].  One workgroup per image on a
  * reduction tree that depends on T alone (thread t of 256: rows t, t + 256, ... ascending; wave butterfly; the four

@@ -95,6 +95,11 @@ class SampleParams(ctypes.Structure):
     _fields_ = [('temp', c_f32), ('top_k', c_i32), ('top_p_q', ctypes.c_uint32)]
 
 
+class ScoreOut(ctypes.Structure):
+    """struct t2h_score_out (include/t2h_hip.h)."""
+    _fields_ = [('targets', c_vp), ('rank', c_vp)]
+
+
 class RoutedSampleArgs(ctypes.Structure):
     """struct t2h_routed_sample_args (include/t2h_hip.h)."""
     _fields_ = [
@@ -152,6 +157,9 @@ SIGNATURES = {
     't2h_logp_summary': (ctypes.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     't2h_truncation_threshold': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, ctypes.c_uint32, c_i32, c_vp, c_vp, c_vp]),
     't2h_sample_heads_per_sample': (ctypes.c_int, [ctypes.POINTER(SampleHeadsArgs), c_vp, c_i32, c_vp]),
+    't2h_score_heads': (ctypes.c_int, [ctypes.POINTER(SampleHeadsArgs), ctypes.POINTER(ScoreOut), c_vp]),
+    't2h_score_heads_per_sample': (ctypes.c_int, [ctypes.POINTER(SampleHeadsArgs), ctypes.POINTER(ScoreOut), c_vp, c_i32,
+                                                  c_vp]),
     't2h_confidence_tail_per_sample': (ctypes.c_int, [ctypes.POINTER(ConfidenceTailArgs), c_vp, c_i32, c_vp]),
     't2h_confidence_commit_per_sample': (ctypes.c_int, [ctypes.POINTER(ConfidenceCommitArgs), c_vp]),
     't2h_truncation_threshold_per_row': (ctypes.c_int, [c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),

@@ -768,6 +768,53 @@ __global__ __launch_bounds__(SH_THREADS) void sample_pick_kernel(const t2h_sampl
   }
 }
 
+// ---- scoring a given token map: the second launch of the two-launch tail with the row's token READ
+// from targets[head][row] instead of raced for.  The log-probability is formed by the functions, in the order, of the LOGP
+// tail above (row_max, row_logsum, then (l_tok - max) - logf(se) on thread 0), so a token that sample_pick_kernel drew
+// scores the bits that launch wrote.  rank = the number of classes with a strictly greater logit: an integer count (wave
+// butterfly, the waves through LDS), so it does not depend on any order.  No noise is read.  A token outside
+// [0, n_class) indexes nothing: logp = NaN, rank = -1, x_t / out_idx untouched.
+__global__ __launch_bounds__(SH_THREADS) void score_pick_kernel(const t2h_sample_heads_args a, const float* __restrict__ ws,
+                                                                const int64_t* __restrict__ targets,
+                                                                int32_t* __restrict__ rank) {
+  constexpr int NW = SH_THREADS / 64;
+  __shared__ float red[NW];
+  __shared__ int cnt[NW];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int slot = blockIdx.x, row = a.rows[slot];
+  const int head = (int)a.tex[row];
+  const int64_t tok = targets[(int64_t)head * a.n + row];
+  if (tok < 0 || tok >= a.n_class) {  // (uniform over the workgroup: nobody reaches a barrier)
+    if (tid == 0) {
+      a.logp[row] = __builtin_nanf("");
+      if (rank) rank[row] = -1;
+    }
+    return;
+  }
+  const float* lg = ws + (int64_t)slot * a.n_class;
+  const float mx = row_max<SH_THREADS>(lg, a.n_class, tid, red, lane, wave);
+  const float se = row_logsum<SH_THREADS>(lg, a.n_class, mx, tid, red, lane, wave);
+  const float lt = lg[tok];
+  if (tid == 0) {
+    a.logp[row] = (lt - mx) - logf(se);
+    a.x_t[row] = tok + (int64_t)a.n_class * head;
+    a.out_idx[(int64_t)head * a.n + row] = tok;
+  }
+  if (rank) {  // (uniform over the workgroup)
+    int c = 0;
+    for (int j = tid; j < a.n_class; j += SH_THREADS) c += lg[j] > lt ? 1 : 0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    if (lane == 0) cnt[wave] = c;
+    __syncthreads();
+    if (tid == 0) {
+      int tot = 0;
+      for (int k = 0; k < NW; ++k) tot += cnt[k];
+      rank[row] = tot;
+    }
+  }
+}
+
 // All heads in one launch: one workgroup per CHANGED token (compact list from
 // unmask_step), which picks the head / noise tensor of its own texture.
 template <int C, bool TRUNC, bool PER_SAMPLE, bool LOGP>
@@ -1376,6 +1423,41 @@ extern "C" int t2h_sample_heads_per_sample(const t2h_sample_heads_args* args, co
                                            int32_t rows_per_sample, void* stream) {
   T2H_REQUIRE(params != nullptr, "t2h_sample_heads_per_sample: params is NULL");
   return sample_heads_launch(args, params, rows_per_sample, stream);
+}
+
+// Scoring: launch 1 is the sampling call's (the same instantiation and grid, so the same logits), launch 2 reads the
+// token.  The noise and truncation fields of `args` are not read.
+static int score_heads_launch(const char* name, const t2h_sample_heads_args* args, const t2h_score_out* score,
+                              const t2h_sample_params* params, int32_t T, void* stream) {
+  T2H_REQUIRE(args != nullptr && score != nullptr, "%s: args / score is NULL", name);
+  t2h_sample_heads_args a = *args;
+  if (params) a.temp = 1.f;
+  T2H_REQUIRE(a.hidden && a.lnf_gamma && a.lnf_beta && a.w_heads && a.rows && a.tex && a.x_t && a.out_idx,
+              "%s: NULL pointer", name);
+  T2H_REQUIRE(a.logits_ws != nullptr && a.logp != nullptr && score->targets != nullptr,
+              "%s: logits_ws, logp and targets are required (the two-launch form only)", name);
+  T2H_REQUIRE(a.n > 0 && a.n_class > 0 && a.temp > 0.f && a.n_rows >= 0 && a.n_heads > 0 && a.n_heads <= T2H_MAX_HEADS,
+              "%s: bad arguments", name);
+  T2H_REQUIRE(a.C == 512, "%s: C=%d unsupported (512)", name, a.C);
+  if (params) T2H_PER_SAMPLE_REQUIRE("t2h_score_heads_per_sample", params, T, a.n, a.n_class);
+  if (a.n_rows == 0) return T2H_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL((params ? sample_logits_kernel<512, true> : sample_logits_kernel<512, false>),
+                     dim3(a.n_rows * SL_SPLIT), dim3(SL_THREADS), 0, s, a, a.logits_ws, params, T);
+  hipLaunchKernelGGL(score_pick_kernel, dim3(a.n_rows), dim3(SH_THREADS), 0, s, a, a.logits_ws, score->targets,
+                     score->rank);
+  T2H_CHECK_LAUNCH(name);
+  return T2H_OK;
+}
+
+extern "C" int t2h_score_heads(const t2h_sample_heads_args* args, const t2h_score_out* score, void* stream) {
+  return score_heads_launch("t2h_score_heads", args, score, nullptr, 0, stream);
+}
+
+extern "C" int t2h_score_heads_per_sample(const t2h_sample_heads_args* args, const t2h_score_out* score,
+                                          const t2h_sample_params* params, int32_t rows_per_sample, void* stream) {
+  T2H_REQUIRE(params != nullptr, "t2h_score_heads_per_sample: params is NULL");
+  return score_heads_launch("t2h_score_heads_per_sample", args, score, params, rows_per_sample, stream);
 }
 
 extern "C" int t2h_q_sample(const int64_t* x0, const float* u, const int64_t* t, int32_t num_timesteps,

@@ -725,11 +725,12 @@ def _initial_state(init, tex_tok, n_books, mask_id, n_class, x_t=None, out=None)
 
 
 def _round(net, x_t, out, segm_tok, tex_tok, rows, n_rows, noise, temp, logits_ws, trunc_kw, defer=True, active=None,
-           logp=None):
+           logp=None, targets=None, rank=None):
     """One round of the reference's loop: the transformer on x_t (defer: the last layer's tail on the listed rows only,
     and only the first `active` samples), then the tokens of the first n_rows of `rows` drawn into x_t / out.  temp /
     trunc_kw: the scalar controls (_trunc_kw), or temp None and the per-image table (_per_image_kw).  logp (f32 [B*T],
-    None = off): the drawn rows' log-probabilities (ops.sample_heads)."""
+    None = off): the drawn rows' log-probabilities (ops.sample_heads).  targets (int64 [n_books, B*T], None = off; needs
+    logp): scoring -- the listed rows take their token from it instead of drawing one; rank (int32 [B*T], optional)."""
     compact = False
     if defer:
         net.hidden(x_t, segm_tok, tex_tok, defer_tail=True, active=active)
@@ -738,6 +739,8 @@ def _round(net, x_t, out, segm_tok, tex_tok, rows, n_rows, noise, temp, logits_w
         hidden = net.hidden(x_t, segm_tok, tex_tok)
     if logp is not None:  # (without it: today's call, keyword for keyword)
         trunc_kw = dict(trunc_kw, logp=logp)
+    if targets is not None:
+        trunc_kw = dict(trunc_kw, targets=targets, rank=rank)
     ops.sample_heads(hidden, *net.final_norm_and_heads(), {}, rows, n_rows, tex_tok.view(-1), temp, x_t, out,
                      row_noise=noise, hidden_compact=compact, logits_ws=logits_ws, **trunc_kw)
 
@@ -752,7 +755,7 @@ class RoundGraph:
     (prepare), replayed for every round of every run."""
 
     def __init__(self, net, B, T, steps, maxr, n_books, n_class, temp, mask_id, dev, trunc=(0, 0), per_image=False,
-                 logp=False):
+                 logp=False, score=None):
         i64 = lambda *s: torch.empty(s, dtype=torch.int64, device=dev)
         i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)
         # (a weak reference: net._graphs owns this object -- a strong one would make a cycle that only the cyclic
@@ -774,7 +777,11 @@ class RoundGraph:
         self.logits_ws = torch.empty((maxr, n_class), dtype=torch.float32, device=dev)
         # per-token log-probabilities (return_logp): a persistent buffer the captured tail points to, NaN-filled by run()
         # beside the initial state; None = the tail without them (part of the graph key)
-        self.logp = torch.empty(B * T, dtype=torch.float32, device=dev) if logp else None
+        self.logp = torch.empty(B * T, dtype=torch.float32, device=dev) if (logp or score) else None
+        # scoring (score_tokens; `score` = the key's trailing element): the map to score, filled by run() beside the
+        # initial state in the schedule's sample order, and the optional rank output (-1 = never scored)
+        self.targets = i64(n_books, B * T) if score else None
+        self.rank = i32(B * T) if score == SCORE_RANK else None
         self.stream = torch.cuda.Stream(device=dev)
         self.B = B
         self.graphs = {}  # samples still running (a prefix of the batch, schedule.leave_order) -> captured round
@@ -787,8 +794,10 @@ class RoundGraph:
         loop.  One eager round on a valid dummy state first (it
         sizes every lazily allocated workspace); a capture itself executes nothing.  Call on self.stream."""
         _initial_state(None, self.tex, self.out.shape[0], self.mask_id, self.n_class, self.x_t, self.out)
-        for t in (self.segm, self.tex, self.rows_tbl, self.offs_tbl, self.rng_tbl, self.round_ctr, self.seed):
-            t.zero_()
+        for t in (self.segm, self.tex, self.rows_tbl, self.offs_tbl, self.rng_tbl, self.round_ctr, self.seed,
+                  self.targets):
+            if t is not None:
+                t.zero_()
         self.body(self.B)
         self.stream.synchronize()
         for k in sorted(counts, reverse=True):
@@ -801,7 +810,7 @@ class RoundGraph:
                              self.cur_rng, self.maxr)
         _round(self._net(), self.x_t, self.out, self.segm, self.tex, self.cur_rows, self.maxr,
                ('philox', self.seed, self.cur_offs, self.cur_rng), self.temp, self.logits_ws, self.trunc, active=k,
-               logp=self.logp)
+               logp=self.logp, targets=self.targets, rank=self.rank)
 
     def capture(self, k):
         g = torch.cuda.CUDAGraph()
@@ -818,11 +827,12 @@ class RoundGraph:
                 gc.enable()
         self.graphs[k] = g
 
-    def run(self, sched, segm_tok, tex_tok, init=None, params=None):
+    def run(self, sched, segm_tok, tex_tok, init=None, params=None, targets=None):
         """All rounds of one run on this graph's stream; returns `out` (valid once the caller's stream
         has waited, which this does).  init = (src_lists, keep) in the schedule's sample order (region editing):
         x_t / out start from t2h_edit_prefill instead of all-masked -- before the replays, outside any capture.
-        params (a per-image graph): the run's table (ops.SAMPLE_PARAMS_DTYPE [B]) in the schedule's sample order."""
+        params (a per-image graph): the run's table (ops.SAMPLE_PARAMS_DTYPE [B]) in the schedule's sample order.
+        targets (a scoring graph): the map to score, int64 [n_books, B*T] in the schedule's sample order."""
         order, offs, rng_rows = sched.host
         tables = schedule.RoundTables(order, offs, sched.start, self.maxr, per_row32=rng_rows if rng_rows is not None else order)
         R, rows_tbl, offs_tbl = tables.n_rounds, tables.rows_tbl, tables.val_tbl
@@ -845,6 +855,10 @@ class RoundGraph:
             _initial_state(init, self.tex, self.out.shape[0], self.mask_id, self.n_class, self.x_t, self.out)
             if self.logp is not None:
                 self.logp.fill_(float('nan'))  # (a row that is never drawn keeps it)
+            if self.targets is not None:
+                self.targets.copy_(targets)
+            if self.rank is not None:
+                self.rank.fill_(-1)
             self.round_ctr.zero_()
             self.seed.fill_(schedule.as_int64(sched.seed))  # (a uint64 seed >= 2^63 in its two's-complement form)
             for r in range(R):
@@ -867,19 +881,25 @@ def _per_image_kw(params, T):
     return dict(params=params, rows_per_sample=int(T))
 
 
-def round_graph_key_per_image(B, T, sample_steps, maxr, mask_id, n_books, x8, logp=False):
+SCORE, SCORE_RANK = 'score', 'score+rank'  # the trailing key element of a scoring graph: without / with the rank output
+
+
+def round_graph_key_per_image(B, T, sample_steps, maxr, mask_id, n_books, x8, logp=False, score=None):
     """The key of the captured rounds of per-image runs: the table is read from a buffer of the graph, so neither
     temperatures nor truncation settings are held by value -- runs with different values share the captures.  logp
-    (the tail that also writes log-probabilities): one more trailing element, absent without it."""
-    return (B, T, sample_steps, maxr, int(mask_id), n_books, bool(x8), 'per-sample') + (('logp', ) if logp else ())
+    (the tail that also writes log-probabilities): one more trailing element, absent without it.  score (SCORE /
+    SCORE_RANK: the tail that reads its tokens from a target map, score_tokens): likewise."""
+    return ((B, T, sample_steps, maxr, int(mask_id), n_books, bool(x8), 'per-sample') + (('logp', ) if logp else ()) +
+            ((score, ) if score else ()))
 
 
-def round_graph_key(B, T, sample_steps, maxr, temp, mask_id, n_books, x8, trunc=(0, 0), logp=False):
+def round_graph_key(B, T, sample_steps, maxr, temp, mask_id, n_books, x8, trunc=(0, 0), logp=False, score=None):
     """What a captured round (RoundGraph) holds BY VALUE: two calls share a graph iff this key is equal.  logp (the tail
     that also writes log-probabilities): one more trailing element, absent without it -- the keys, and so the captures,
-    of runs without it are what they always were."""
+    of runs without it are what they always were.  score (SCORE / SCORE_RANK: the scoring tail, score_tokens): one more
+    trailing element by the same rule."""
     return ((B, T, sample_steps, maxr, float(temp), int(mask_id), n_books, bool(x8), int(trunc[0]), int(trunc[1])) +
-            (('logp', ) if logp else ()))
+            (('logp', ) if logp else ()) + ((score, ) if score else ()))
 
 
 def sample_tokens(net, segm_tok, tex_tok, sample_steps, mask_id, temp=1.0, noise=None,
@@ -918,6 +938,52 @@ def sample_tokens(net, segm_tok, tex_tok, sample_steps, mask_id, temp=1.0, noise
     Test hooks, called after each round and allowed to overwrite x_t in place (teacher forcing):
     round_hook(r, steps, x_t, out) with steps[b] = the step sample b just took (0 = idle);
     step_hook(t, x_t, out) (compact=False only; steps that change no token are skipped)."""
+    return _token_loop(net, segm_tok, tex_tok, sample_steps, mask_id, temp, noise, n_books, step_hook, round_hook, compact,
+                       init, top_k, top_p, return_logp)
+
+
+def _target_check(targets, tex_flat, n_class, T):
+    """Scoring: every row's target under its own texture must be a class -- t2h_edit_prefill's check-only form with an
+    all-ones keep; raises T2HError naming the first offending (sample, row), before the generator has moved."""
+    ones = torch.ones(tex_flat.numel(), dtype=torch.uint8, device=tex_flat.device)
+    e = int(ops.edit_prefill(targets, tex_flat, ones, 0, n_class).cpu()[0])
+    if e:
+        r = tex_flat.numel() - e
+        raise _lib.T2HError(f'score: token row {r % T} of sample {r // T} has no index in [0, {n_class}) under the current '
+                            'texture map in the token map to score')
+
+
+def score_tokens(net, segm_tok, tex_tok, sample_steps, mask_id, targets, temp=1.0, noise=None, n_books=18, keep=None,
+                 compact=None, round_hook=None, return_rank=False):
+    """Teacher-forced per-token log-probabilities of a GIVEN token map along sample_tokens' own path.
+
+    targets int64 [n_books, B*T] (the layout sample_tokens returns; row r's token is targets[tex[r]][r]).  The loop is
+    sample_tokens' -- the same schedule, rounds, sample reordering and eager / graph decision -- except that a row's
+    token is read from `targets` instead of drawn, so that the next round sees the state sampling that map would have
+    produced.  Returns logp float32 [B*T] in the caller's sample order: the natural-log probability of the row's target
+    under the full softmax of logits / temp at the round the schedule unmasks it; with return_rank (logp, rank), rank
+    int32 [B*T] = the number of classes with a strictly greater logit (0 = the mode).
+
+    keep (uint8 [B*T]): those rows start as their target token (init = (targets, keep)), are not scored -- NaN, rank -1
+    -- and the rest is scored conditionally on them.  temp: a scalar, or one value per image.  There is no top_k /
+    top_p: truncation never changed the distribution.
+
+    Every row's own-texture target must lie in [0, n_class): T2HError (first offending (sample, row)) before the
+    generator has moved.  The generator is consumed exactly as sample_tokens with the same init consumes it, the
+    offsets of the exponential draws that are never made included: a map that sample_tokens(return_logp=True) drew at
+    generator state G, scored at state G, returns that call's logp bits."""
+    if tuple(targets.shape) != (n_books, segm_tok.numel()) or targets.dtype != torch.int64:
+        raise ValueError(f'targets: int64 [{n_books}, {segm_tok.numel()}] expected, got {targets.dtype} {tuple(targets.shape)}')
+    targets = targets.contiguous()
+    return _token_loop(net, segm_tok, tex_tok, sample_steps, mask_id, temp, noise, n_books, None, round_hook, compact,
+                       None if keep is None else (targets, keep), None, None, True,
+                       score=(targets, SCORE_RANK if return_rank else SCORE))
+
+
+def _token_loop(net, segm_tok, tex_tok, sample_steps, mask_id, temp, noise, n_books, step_hook, round_hook, compact, init,
+                top_k, top_p, return_logp, score=None):
+    """The loop of sample_tokens (see there).  score = (targets, SCORE or SCORE_RANK): score_tokens -- every round's
+    tail reads its tokens from `targets`; returns logp, or (logp, rank)."""
     B, T = segm_tok.shape
     dev, n = segm_tok.device, B * T
     if compact is None:
@@ -926,6 +992,10 @@ def sample_tokens(net, segm_tok, tex_tok, sample_steps, mask_id, temp=1.0, noise
         raise ValueError('step_hook needs compact=False (samples are at different steps in a compact round)')
     noise, n_class, sp, tex_flat, tex_host = _begin_run(net, tex_tok, n_books, noise, init, temp, top_k, top_p)
     table = sp.table
+    targets = score_kind = None
+    if score is not None:
+        targets, score_kind = score
+        _target_check(targets, tex_flat, n_class, T)
     # finished samples leave the batch (T2H_SHRINK_BATCH=0 opts out; hooks see the batch in its own order)
     shrink = (compact and step_hook is None and round_hook is None and os.environ.get('T2H_SHRINK_BATCH', '1') != '0')
     sched = _schedule(tex_flat, tex_host, B, sample_steps, n_books, n_class, noise, compact, shrink, init)
@@ -940,6 +1010,8 @@ def sample_tokens(net, segm_tok, tex_tok, sample_steps, mask_id, temp=1.0, noise
         segm_tok, tex_tok = segm_tok[perm_t].contiguous(), tex_tok[perm_t].contiguous()
         if init is not None:  # the initial state in the schedule's sample order, like segm_tok / tex_tok
             init = (init[0].view(-1, B, T)[:, perm_t].reshape(-1, n).contiguous(), init[1].view(B, T)[perm_t].reshape(n))
+        if targets is not None:  # the map to score, likewise
+            targets = targets.view(-1, B, T)[:, perm_t].reshape(-1, n).contiguous()
         if table is not None:  # the kernels index the table by the sample's position in the batch THEY see
             table = table[sched.perm]
         caller_rows = torch.from_numpy(schedule.in_caller_order(sched.perm, B, T)).to(dev)
@@ -958,30 +1030,38 @@ def sample_tokens(net, segm_tok, tex_tok, sample_steps, mask_id, temp=1.0, noise
         maxr = min(net.TRIM_MAX_ROWS, max(16, 1 << (int(sched.max_rows) - 1).bit_length()))
         net._buffers(n, net.desc['C'], dev)  # (a change of batch size drops the graphs of the old buffers)
         if table is None:
-            key = round_graph_key(B, T, sample_steps, maxr, temp, mask_id, n_books, net.x8, sp.trunc, logp=return_logp)
+            key = round_graph_key(B, T, sample_steps, maxr, temp, mask_id, n_books, net.x8, sp.trunc,
+                                  logp=return_logp and score is None, score=score_kind)
         else:
-            key = round_graph_key_per_image(B, T, sample_steps, maxr, mask_id, n_books, net.x8, logp=return_logp)
+            key = round_graph_key_per_image(B, T, sample_steps, maxr, mask_id, n_books, net.x8,
+                                            logp=return_logp and score is None, score=score_kind)
         if key not in net._graphs:
             net._graphs[key] = RoundGraph(net, B, T, sample_steps, maxr, n_books, n_class, temp, mask_id, dev,
-                                          trunc=sp.trunc, per_image=table is not None, logp=return_logp)
+                                          trunc=sp.trunc, per_image=table is not None, logp=return_logp, score=score_kind)
         graph = net._graphs[key]
-        out = in_batch_order(graph.run(sched, segm_tok, tex_tok, init=init, params=table).clone())
+        out = in_batch_order(graph.run(sched, segm_tok, tex_tok, init=init, params=table, targets=targets).clone())
+        if score is not None:
+            logp = in_batch_order(graph.logp.clone())
+            return (logp, in_batch_order(graph.rank.clone())) if score_kind == SCORE_RANK else logp
         return (out, in_batch_order(graph.logp.clone())) if return_logp else out
     tail_kw = _trunc_kw(sp.trunc) if table is None else _per_image_kw(ops.sample_params_tensor(table, dev), T)
     x_t, out, _ = _initial_state(init, tex_tok, n_books, mask_id, n_class)
     logp = torch.full((n, ), float('nan'), dtype=torch.float32, device=dev) if return_logp else None
+    rank = torch.full((n, ), -1, dtype=torch.int32, device=dev) if score_kind == SCORE_RANK else None
     logits_ws = torch.empty((max(sched.max_rows, 1), n_class), dtype=torch.float32, device=dev)
     for r in range(sched.n_rounds):
         lo, hi = int(sched.start[r]), int(sched.start[r + 1])
         k = int(sched.active[r]) if sched.active is not None else None
         _round(net, x_t, out, segm_tok, tex_tok, sched.rows[lo:hi], hi - lo, sched.row_noise(lo, hi), sp.temp, logits_ws,
-               tail_kw, defer, k, logp)
+               tail_kw, defer, k, logp, targets, rank)
         if round_hook is not None:
             round_hook(r, sched.round_steps[r], x_t, out)
         if step_hook is not None:
             step_hook(int(sched.round_steps[r].max()), x_t, out)
     if net.split:
         check_split_overflow('index sampler')
+    if score is not None:
+        return (in_batch_order(logp), in_batch_order(rank)) if rank is not None else in_batch_order(logp)
     return (in_batch_order(out), in_batch_order(logp)) if return_logp else in_batch_order(out)
 
 

@@ -10,6 +10,7 @@ text2human_amd.engine, batched over images, with no PyTorch compute fallback.
 """
 import collections
 import logging
+import numbers
 import os
 
 import numpy as np
@@ -146,11 +147,13 @@ class BaseSampleModel():
         """(top_k, top_p) of the options `sample_top_k` / `sample_top_p` (None, None: off)."""
         return options.sampling_truncation(self.opt)
 
-    def _sample(self, temp, sample_steps, init=None, confidence=None, top_k=None, top_p=None, return_logp=False):
+    def _sample(self, temp, sample_steps, init=None, confidence=None, top_k=None, top_p=None, return_logp=False,
+                score=None):
         """sample_fn's body (init: engine.sample_tokens' initial state of a region edit; confidence = (rounds,
         choice_temp): engine.sample_tokens_confidence instead of the reference's loop; top_k / top_p: truncated
         sampling, passed to every attempt of the fall-back chain below; return_logp: -> (lists, logp [B, 512]), the
-        log-probabilities of the attempt that produced the tokens)."""
+        log-probabilities of the attempt that produced the tokens; score = (targets [18, B*512], keep or None,
+        return_rank): engine.score_tokens on that map instead of a draw -> logp [B, 512], or (logp, rank))."""
         logp_kw = dict(return_logp=True) if return_logp else {}  # (without it: today's calls, keyword for keyword)
         ops.sampling_params(self.batch_size, temp, top_k, top_p)  # (raises before anything is evaluated or drawn)
         tex_tok = self._texture_tokens(self.texture_mask)
@@ -165,7 +168,11 @@ class BaseSampleModel():
         try:
             for _ in range(3):  # x8 planes -> fp16 planes -> exact fp32, each at most once
                 try:
-                    if confidence is not None:
+                    if score is not None:
+                        out = engine.score_tokens(net, self.segm_tokens.contiguous(), tex_tok, sample_steps, self.mask_id,
+                                                  score[0], temp=temp, noise=self.noise, keep=score[1],
+                                                  return_rank=score[2])
+                    elif confidence is not None:
                         out = engine.sample_tokens_confidence(net, self.segm_tokens.contiguous(), tex_tok, self.mask_id,
                                                               rounds=confidence[0], temp=temp,
                                                               choice_temp=confidence[1], noise=self.noise, init=init,
@@ -191,6 +198,8 @@ class BaseSampleModel():
         finally:
             self.sampler_fn.x8 = x8_was
         b = self.batch_size
+        if score is not None:
+            return (out[0].view(b, -1), out[1].view(b, -1)) if score[2] else out.view(b, -1)
         if return_logp:
             out, logp = out
             return [out[i].view(b, -1) for i in range(out.shape[0])], logp.view(b, -1)
@@ -292,6 +301,34 @@ class BaseSampleModel():
         confidence = self._confidence_args(rounds, choice_temp) if order == 'confidence' else None
         return self._sample(temp, sample_steps or self.sample_steps, init=init, confidence=confidence, top_k=top_k,
                             top_p=top_p, return_logp=return_logp)
+
+    @torch.no_grad()
+    def score_fn(self, top_indices_list, keep=None, temp=1.0, sample_steps=None, return_rank=False, summary=False):
+        """Teacher-forced per-token log-probabilities of a GIVEN token map (opt-in): how likely the
+        sampler holds `top_indices_list` (18 x int64 [B, 512] or [18, B*512], as resample_fn / decode_indices accept:
+        an earlier result, an edit, a candidate, a photo's top_encode indices) along sample_fn's own path -- the same
+        schedule from the current generator state, every row's token read from the map instead of drawn.  -> logp
+        float32 [B, 512]: the log-probability of the row's token under the full softmax of logits / temp at the round
+        that unmasks it.  A map that sample_fn(return_logp=True) drew at generator state G, scored at state G with the
+        same temp / sample_steps, returns that call's logp bits; the generator ends where sample_fn leaves it.
+        keep [B, 512] (as in resample_fn; region_keep's output): those rows are given, not scored (NaN, rank -1); the
+        rest is scored conditionally on them, as resample_fn draws them.  temp: a scalar or one value per image.
+        return_rank: also rank int32 [B, 512] = the number of classes the model held strictly more likely (0 = its
+        mode).  summary: also the per-image (sum, count, min) of the scored rows (t2h_logp_summary).  Returns logp, or
+        the tuple (logp[, rank][, (sum, count, min)]).  Every row's token under the current texture map must be a class
+        index: T2HError naming the first offending (sample, row), nothing drawn."""
+        # (everything below raises before anything is evaluated or drawn)
+        if not options.is_per_image(temp) and (isinstance(temp, bool) or not isinstance(temp, numbers.Real) or
+                                               not 0.0 < float(temp) < float('inf')):
+            raise ValueError(f'score_fn: temp must be a finite number > 0, got {temp!r}')
+        ops.sampling_params(self.batch_size, temp)  # (a per-image sequence: its length and every entry)
+        targets = self._token_lists(top_indices_list, 'score_fn')
+        keep = None if keep is None else self._keep_rows(keep)
+        out = self._sample(temp, sample_steps or self.sample_steps, score=(targets, keep, bool(return_rank)))
+        res = list(out) if return_rank else [out]
+        if summary:
+            res.append(ops.logp_summary(res[0].contiguous()))
+        return res[0] if len(res) == 1 else tuple(res)
 
     @torch.no_grad()
     def edit_and_refine(self, top_indices_list, region=None, labels=None, bot_indices_list=None, save_dir=None,

@@ -976,7 +976,7 @@ def _philox_fields(a, numel, device, **fields):
 
 def sample_heads(hidden, lnf_g, lnf_b, w_heads, expo_by_head, rows, n_rows, tex, temp, x_t, out_idx, split=True,
                  philox=None, hidden_compact=False, row_noise=None, logits_ws=None, top_k=0, top_p=1.0, params=None,
-                 rows_per_sample=None, logp=None):
+                 rows_per_sample=None, logp=None, targets=None, rank=None):
     """All heads in one launch: `rows` (int32, first n_rows valid) are the changed token
     rows, expo_by_head {head: [n, n_class] Exp(1) draw}, w_heads [n_heads, n_class, C],
     out_idx [n_heads, n].  philox = (seed, {head: generator offset}): the noise of the listed heads is
@@ -989,8 +989,22 @@ def sample_heads(hidden, lnf_g, lnf_b, w_heads, expo_by_head, rows, n_rows, tex,
     params (sample_params_tensor) + rows_per_sample: per-image controls (t2h_sample_heads_per_sample) -- row r is drawn
     with params[r // rows_per_sample]; temp / top_k / top_p are then not read.
     logp (f32, >= n elements, indexed by token row like x_t; None = off, the kernels without it): every listed row
-    also gets the log-probability of its token under the full softmax of logits / temp."""
+    also gets the log-probability of its token under the full softmax of logits / temp.
+    targets (int64 [n_heads, n], the layout of out_idx; None = off): scoring (t2h_score_heads[_per_sample], DESIGN.md
+    4.6g) -- the token of a listed row is read from targets[tex[row]][row] instead of drawn, no noise is read, logp is
+    required; rank (int32, >= n elements, optional): the number of classes with a strictly greater logit."""
     _chk_f32(hidden, lnf_g, lnf_b, w_heads, *expo_by_head.values())
+    score = None
+    if targets is not None:
+        _chk_i64(targets)
+        assert logp is not None and targets.is_contiguous() and tuple(targets.shape) == tuple(out_idx.shape)
+        score = _lib.ScoreOut()
+        score.targets = targets.data_ptr()
+        if rank is not None:
+            assert rank.dtype == torch.int32 and rank.is_cuda and rank.is_contiguous() and rank.numel() >= out_idx.shape[1]
+            score.rank = rank.data_ptr()
+    else:
+        assert rank is None
     if logp is not None:
         _chk_f32(logp)
         assert logp.is_contiguous() and logp.numel() >= out_idx.shape[1], (tuple(logp.shape), tuple(out_idx.shape))
@@ -1014,7 +1028,7 @@ def sample_heads(hidden, lnf_g, lnf_b, w_heads, expo_by_head, rows, n_rows, tex,
     a.top_k, a.top_p_q = trunc
     if logp is not None:
         a.logp = logp.data_ptr()
-    if (split or philox is not None or hidden_compact or row_noise is not None) and n_rows > 0:
+    if (split or philox is not None or hidden_compact or row_noise is not None or score is not None) and n_rows > 0:
         # logits scratch: 8 workgroups per row share the weight stream
         ws = logits_ws if logits_ws is not None else torch.empty((int(n_rows), n_class), device=hidden.device,
                                                                  dtype=torch.float32)
@@ -1040,6 +1054,12 @@ def sample_heads(hidden, lnf_g, lnf_b, w_heads, expo_by_head, rows, n_rows, tex,
         _philox_fields(a, n * n_class, hidden.device, philox_seed=philox[0])
         for h, off in philox[1].items():
             a.philox_offset[h] = int(off)
+    if score is not None:
+        if params is not None:
+            T = _chk_params(params, rows_per_sample, n)
+            return check(_lib.load().t2h_score_heads_per_sample(ctypes.byref(a), ctypes.byref(score), _p(params), T,
+                                                                _stream()), 't2h_score_heads_per_sample')
+        return check(_lib.load().t2h_score_heads(ctypes.byref(a), ctypes.byref(score), _stream()), 't2h_score_heads')
     if params is not None:
         T = _chk_params(params, rows_per_sample, n)
         return check(_lib.load().t2h_sample_heads_per_sample(ctypes.byref(a), _p(params), T, _stream()),
