@@ -193,6 +193,11 @@ typedef struct t2h_gemm_split_args {
    * holds ksplit * M rows; bias and residual go with slice 0); the caller sums the slices in a fixed order.  Built
    * for the proj / fc2 experiment of round 6 (profiles/r06_fc2_128x128_splitk.log); the dispatcher never picks it. */
   int32_t ksplit;
+  /* > 0: the tile configuration is picked as for a problem of cfg_rows rows instead of M (0 = off).  A tile
+   * configuration fixes the order in which an output element's K products are summed, so two calls that run on the
+   * same configuration give a row the same bits however many rows each call has: a caller that needs a row's result
+   * not to depend on the batch it sits in (per-image seeds) names one row count for all its calls. */
+  int32_t cfg_rows;
 } t2h_gemm_split_args;
 
 int t2h_gemm_split_f32(const t2h_gemm_split_args* args, void* stream);
@@ -249,6 +254,10 @@ int t2h_mha_split_x8_f32(const uint16_t* qk_split, int32_t ld_cols, const uint16
  * walk all keys (B >= 16: no merge, K / Vt tiles shared by eight waves).  Tuning / tests (thread-local): 1 = all
  * keys, 2 = key halves, 0 = automatic; returns the old value. */
 int t2h_mha_split_force_form(int form);
+/* the form (1 all keys / 2 key halves) t2h_mha_split_f32 / t2h_mha_split_x8_f32 pick by themselves for a problem of B
+ * samples; nothing is launched.  A caller that needs a sample's bits not to depend on the batch (per-image seeds,
+ * DESIGN.md 4.6h) forces the form of B = 1. */
+int t2h_mha_split_form(int32_t B, int32_t T, int32_t n_head);
 
 /* ------------------------------------------------------ normalisation ------
  * LayerNorm over the last dim (eps 1e-5): transformer_arch.py:80-81,93-95,231,270 */
@@ -359,6 +368,15 @@ typedef struct t2h_sample_heads_args {
    * (the kernels without it) */
   int32_t top_k;
   uint32_t top_p_q;
+  /* per-image seeds (NULL = off: the kernels without it).  philox_seed_img[n / img_rows]: one seed per
+   * image, in the order the batch has on the device; img_rows = token rows per image (T).  Listed row r is then drawn with
+   * seed philox_seed_img[r / img_rows] (philox_seed / philox_seed_dev are not read) and its noise is row r % img_rows of
+   * its OWN image's [img_rows, n_class] exponential_ draw -- philox_grid_threads is that draw's geometry -- at
+   * row_philox_offset[i]; rng_rows[i], if given, still names the noise row.  Needs row_philox_offset,
+   * philox_grid_threads and logits_ws.  The scoring entry points draw no noise and do not read these fields.  (They
+   * sit before `logp`, which stays the struct's last field.) */
+  const uint64_t* philox_seed_img;
+  int32_t img_rows;
   /* optional [n], indexed by token row like x_t (NULL = off: the kernels without it): logp[row] = the natural-log
    * probability of the token the row drew under the FULL softmax of its temperature-scaled logits l,
    *   logp = (l_tok - max l) - logf(se),  se = sum_j expf(l_j - max l)  over all n_class classes
@@ -412,6 +430,15 @@ int t2h_unmask_schedule(uint64_t seed, uint64_t offset, uint32_t rand_grid_threa
 int t2h_unmask_schedule_keep(uint64_t seed, uint64_t offset, uint32_t rand_grid_threads, uint32_t rand_inc,
                              uint32_t expo_inc, const int64_t* tex, const uint8_t* keep, int32_t n, int32_t steps,
                              int32_t n_heads, int32_t* step_of_row, uint32_t* head_mask, void* stream);
+/* Per-image seeds: the schedules of B images in one launch, one workgroup per image.  Image b gets what
+ * t2h_unmask_schedule (keep == NULL) / t2h_unmask_schedule_keep writes for its own T rows -- tex + b T, keep + b T --
+ * with seed seeds[b] (device memory, uint64 [B]) from generator offset 0: step_of_row[b T .. b T + T - 1] and
+ * head_mask[b (steps + 1) .. b (steps + 1) + steps], bit for bit.  rand_grid_threads / rand_inc: ATen's geometry of a
+ * T-element draw, expo_inc: of a T * n_class draw.  The images are independent and the steps sequential, so the launch
+ * takes as long as one image's. */
+int t2h_unmask_schedule_batch(const uint64_t* seeds, uint32_t rand_grid_threads, uint32_t rand_inc, uint32_t expo_inc,
+                              const int64_t* tex, const uint8_t* keep, int32_t B, int32_t T, int32_t steps,
+                              int32_t n_heads, int32_t* step_of_row, uint32_t* head_mask, void* stream);
 int t2h_edit_prefill(const int64_t* src_lists, const int64_t* tex, const uint8_t* keep, int64_t mask_id,
                      int64_t* x_t, int64_t* out_lists, uint32_t* err, int32_t n, int32_t n_heads, int32_t n_class,
                      void* stream);

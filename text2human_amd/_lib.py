@@ -44,6 +44,7 @@ class GemmSplitArgs(ctypes.Structure):
         ('M', c_i32), ('N', c_i32), ('K', c_i32), ('ldc', c_i32), ('ldr', c_i32), ('epi_act', c_i32),
         ('Vt', c_vp), ('vt_col0', c_i32), ('vt_T', c_i32), ('vt_hd', c_i32), ('overflow_flag', c_vp),
         ('fmt', c_i32), ('out_fmt', c_i32), ('lo_mul', c_f32), ('out_scale', c_f32), ('ksplit', c_i32),
+        ('cfg_rows', c_i32),
     ]
 
 
@@ -62,6 +63,7 @@ class SampleHeadsArgs(ctypes.Structure):
         ('row_philox_offset', c_vp), ('expo_rows', c_vp), ('expo_slot', c_vp), ('philox_seed_dev', c_vp),
         ('rng_rows', c_vp),
         ('top_k', c_i32), ('top_p_q', ctypes.c_uint32),
+        ('philox_seed_img', c_vp), ('img_rows', c_i32),
         ('logp', c_vp),
     ]
 
@@ -122,6 +124,7 @@ SIGNATURES = {
                                              c_i32, c_i32, c_vp]),
     't2h_conv_split_force_tile': (ctypes.c_int, [ctypes.c_int]),
     't2h_mha_split_force_form': (ctypes.c_int, [ctypes.c_int]),
+    't2h_mha_split_form': (ctypes.c_int, [c_i32, c_i32, c_i32]),
     't2h_split_rows_x8_f32': (ctypes.c_int, [c_vp, c_i32, c_vp, ctypes.c_int64, c_i32, c_f32, c_vp, c_vp]),
     't2h_layernorm_x8_f32': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, c_vp, c_vp]),
     't2h_mha_split_x8_f32': (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_f32, c_i32, c_i32, c_i32, c_vp, c_vp]),
@@ -172,6 +175,8 @@ SIGNATURES = {
                                            ctypes.c_uint32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     't2h_unmask_schedule_keep': (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
                                                 ctypes.c_uint32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    't2h_unmask_schedule_batch': (ctypes.c_int, [c_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp,
+                                                 c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     't2h_edit_prefill': (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
     't2h_region_keep': (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp,
                                        c_vp]),

@@ -655,6 +655,19 @@ thread_local int g_force_mha_form = 0;  // tuning / test hook of the calling thr
 
 }  // namespace
 
+// Which form the dispatcher picks for a problem: rounds of the 256 CUs (one workgroup per CU at a time) x the measured
+// length of a workgroup -- a 256-query workgroup over all keys takes 5 units where a 128-query one over the two key
+// halves takes 3 (profiles/r05_mha_all_keys.log).  B = 8: 256 x 128-query workgroups, one round; B >= 16: all keys.
+static int pick_mha_form(int32_t B, int32_t T, int32_t n_head) {
+  const int64_t wg2 = (int64_t)(T / QB) * n_head * B, wg1 = T % 256 == 0 ? (int64_t)(T / 256) * n_head * B : 0;
+  return (wg1 > 0 && ((wg1 + 255) / 256) * 5 < ((wg2 + 255) / 256) * 3) ? 1 : 2;
+}
+
+extern "C" int t2h_mha_split_form(int32_t B, int32_t T, int32_t n_head) {
+  T2H_REQUIRE(B > 0 && n_head > 0 && T > 0 && T % QB == 0, "t2h_mha_split_form: bad arguments (B=%d T=%d)", B, T);
+  return pick_mha_form(B, T, n_head);
+}
+
 extern "C" int t2h_mha_split_force_form(int form) {
   const int old = g_force_mha_form;
   g_force_mha_form = (form == 1 || form == 2) ? form : 0;
@@ -705,12 +718,9 @@ static int mha_split_launch(const uint16_t* qk_split, int32_t ld_cols, const uin
   dim3 block(512);
   int* ovf = overflow_flag;
   T2H_REQUIRE(ovf != nullptr || y_split == nullptr, "t2h_mha_split_f32: overflow_flag is NULL (needed with y_split)");
-  // Which form: rounds of the 256 CUs (one workgroup per CU at a time) x the measured length of a workgroup -- a
-  // 256-query workgroup over all keys takes 5 units where a 128-query one over the two key halves takes 3
-  // (profiles/r05_mha_all_keys.log).  B = 8: 256 x 128-query workgroups, one round; B >= 16: the all-keys form.
   const int64_t wg2 = (int64_t)(T / QB) * n_head * B, wg1 = T % 256 == 0 ? (int64_t)(T / 256) * n_head * B : 0;
   int form = g_force_mha_form;
-  if (form == 0) form = (wg1 > 0 && ((wg1 + 255) / 256) * 5 < ((wg2 + 255) / 256) * 3) ? 1 : 2;
+  if (form == 0) form = pick_mha_form(B, T, n_head);
   T2H_REQUIRE(form == 2 || wg1 > 0, "t2h_mha_split_f32: the all-keys form needs T %% 256 == 0");
   if (form == 1)
     hipLaunchKernelGGL(mha_split_pipe_kernel<1>, dim3((unsigned)wg1), block, 0, static_cast<hipStream_t>(stream), qk_split,

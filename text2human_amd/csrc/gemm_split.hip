@@ -895,8 +895,10 @@ extern "C" int t2h_gemm_split_force_config(int cfg) {
   return old;
 }
 
-// tile configuration of the dispatcher for a (validated) problem
-static int pick_split_cfg(const t2h_gemm_split_args& a) {
+// tile configuration of the dispatcher for a (validated) problem; cfg_rows > 0: as for a problem of that many rows
+static int pick_split_cfg(const t2h_gemm_split_args& args) {
+  t2h_gemm_split_args a = args;
+  if (a.cfg_rows > 0) a.M = a.cfg_rows;
   int cfg = g_force_split_cfg;
   if (cfg < 0) {
     // measured on MI355X at M = 4096 (tools/gemm_split_bench.py, profiles/): the 4-wave

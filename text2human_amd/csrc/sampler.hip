@@ -581,11 +581,13 @@ __global__ void philox_uniform_kernel(uint64_t seed, uint64_t offset, uint32_t g
 // KEEP (region editing, t2h_unmask_schedule_keep): rows with keep[i] != 0 start unmasked -- they are never drawn,
 // never set a head bit and keep step_of_row = 0; the `rand` draws and the offset recurrence are unchanged.
 constexpr int SCHED_THREADS = 1024, SCHED_MAX_STEPS = 4096;
+// The loop, for one workgroup: the n rows of tex / keep / step_of_row and the steps + 1 words of head_mask it is handed.
 template <bool KEEP>
-__global__ __launch_bounds__(SCHED_THREADS) void unmask_schedule_kernel(
-    uint64_t seed, uint64_t offset, uint32_t rand_grid_threads, uint32_t rand_inc, uint32_t expo_inc,
-    const int64_t* __restrict__ tex, const uint8_t* __restrict__ keep, int n, int steps,
-    int32_t* __restrict__ step_of_row, uint32_t* __restrict__ head_mask) {
+__device__ __forceinline__ void unmask_schedule_rows(uint64_t seed, uint64_t offset, uint32_t rand_grid_threads,
+                                                     uint32_t rand_inc, uint32_t expo_inc,
+                                                     const int64_t* __restrict__ tex, const uint8_t* __restrict__ keep,
+                                                     int n, int steps, int32_t* __restrict__ step_of_row,
+                                                     uint32_t* __restrict__ head_mask) {
   __shared__ uint32_t mask_s[SCHED_MAX_STEPS + 1];  // one word per step: no reset, one barrier per step
   const int tid = threadIdx.x, lane = tid & 63;
   for (int e = tid; e < n; e += SCHED_THREADS) step_of_row[e] = 0;
@@ -610,6 +612,27 @@ __global__ __launch_bounds__(SCHED_THREADS) void unmask_schedule_kernel(
     off += (uint64_t)rand_inc + (uint64_t)__popc(mask_s[t]) * expo_inc;
   }
   for (int t = tid; t <= steps; t += SCHED_THREADS) head_mask[t] = mask_s[t];
+}
+template <bool KEEP>
+__global__ __launch_bounds__(SCHED_THREADS) void unmask_schedule_kernel(
+    uint64_t seed, uint64_t offset, uint32_t rand_grid_threads, uint32_t rand_inc, uint32_t expo_inc,
+    const int64_t* __restrict__ tex, const uint8_t* __restrict__ keep, int n, int steps,
+    int32_t* __restrict__ step_of_row, uint32_t* __restrict__ head_mask) {
+  unmask_schedule_rows<KEEP>(seed, offset, rand_grid_threads, rand_inc, expo_inc, tex, keep, n, steps, step_of_row,
+                             head_mask);
+}
+// Per-image seeds: one workgroup per image runs the loop above on the image's
+// own T rows with the image's own seed from generator offset 0 -- what t2h_unmask_schedule[_keep] writes for a batch that
+// holds this image alone.  The steps are sequential and the images independent: the launch takes as long as one image.
+template <bool KEEP>
+__global__ __launch_bounds__(SCHED_THREADS) void unmask_schedule_batch_kernel(
+    const uint64_t* __restrict__ seeds, uint32_t rand_grid_threads, uint32_t rand_inc, uint32_t expo_inc,
+    const int64_t* __restrict__ tex, const uint8_t* __restrict__ keep, int T, int steps,
+    int32_t* __restrict__ step_of_row, uint32_t* __restrict__ head_mask) {
+  const int64_t r0 = (int64_t)blockIdx.x * T;
+  unmask_schedule_rows<KEEP>(seeds[blockIdx.x], 0, rand_grid_threads, rand_inc, expo_inc, tex + r0,
+                             KEEP ? keep + r0 : nullptr, T, steps, step_of_row + r0,
+                             head_mask + (int64_t)blockIdx.x * (steps + 1));
 }
 
 // ---- region editing: the reference loop started from a partially known state ("Editing a region").
@@ -726,7 +749,10 @@ __global__ __launch_bounds__(SL_THREADS) void sample_logits_kernel(const t2h_sam
   }
 }
 
-template <bool TRUNC, bool PER_SAMPLE, bool LOGP>
+// SEEDED (per-image seeds): the seed of row `row` is philox_seed_img[row / img_rows] and its noise row,
+// unless rng_rows names one, row % img_rows -- the image's own stream, whatever batch it sits in.  The SEEDED = false
+// instances are the code without either.
+template <bool SEEDED, bool TRUNC, bool PER_SAMPLE, bool LOGP>
 __global__ __launch_bounds__(SH_THREADS) void sample_pick_kernel(const t2h_sample_heads_args a, const float* __restrict__ ws,
                                                                  const t2h_sample_params* __restrict__ params, int T) {
   __shared__ float red[2 * (SH_THREADS / 64)];
@@ -744,10 +770,12 @@ __global__ __launch_bounds__(SH_THREADS) void sample_pick_kernel(const t2h_sampl
                     : a.philox_grid_threads ? nullptr
                                             : a.expo[head] + (int64_t)row * a.n_class;
   const uint64_t poff = a.row_philox_offset ? a.row_philox_offset[slot] : a.philox_offset[head];
-  const uint64_t pseed = a.philox_seed_dev ? *a.philox_seed_dev : a.philox_seed;
+  const uint64_t pseed = SEEDED              ? a.philox_seed_img[row / a.img_rows]  // (row is uniform: one scalar load)
+                         : a.philox_seed_dev ? *a.philox_seed_dev
+                                             : a.philox_seed;
   // the element of the reference's [n, n_class] draw this row owns: its row THERE (the host may have reordered the
-  // samples of the batch, rng_rows) -- by default the row itself
-  const int rng_row = a.rng_rows ? a.rng_rows[slot] : row;
+  // samples of the batch, rng_rows) -- by default the row itself, SEEDED: its row in its own image's [T, n_class] draw
+  const int rng_row = a.rng_rows ? a.rng_rows[slot] : SEEDED ? row % a.img_rows : row;
   race best;
   for (int j = tid; j < a.n_class; j += SH_THREADS) {
     if (TRUNC && !(lg[j] >= theta)) continue;
@@ -1396,6 +1424,12 @@ static int sample_heads_launch(const t2h_sample_heads_args* args, const t2h_samp
                   ((a.expo_rows == nullptr && a.row_philox_offset == nullptr) || a.logits_ws != nullptr),
               "t2h_sample_heads: per-row noise (row_philox_offset / expo_rows) needs the two-launch form and, for "
               "offsets, philox_grid_threads");
+  T2H_REQUIRE(a.philox_seed_img == nullptr ||
+                  (a.row_philox_offset != nullptr && a.philox_grid_threads != 0 && a.logits_ws != nullptr),
+              "t2h_sample_heads: per-image seeds (philox_seed_img) need row_philox_offset, philox_grid_threads and the "
+              "two-launch form (logits_ws)");
+  T2H_REQUIRE(a.philox_seed_img == nullptr || (a.img_rows > 0 && a.n % a.img_rows == 0),
+              "t2h_sample_heads: per-image seeds need img_rows=%d > 0 dividing n=%d", (int)a.img_rows, (int)a.n);
   T2H_TRUNC_REQUIRE("t2h_sample_heads", a.top_k, a.top_p_q, a.n_class);
   const bool trunc = trunc_settings(a.n_class, &a.top_k, &a.top_p_q);
   if (params) T2H_PER_SAMPLE_REQUIRE("t2h_sample_heads_per_sample", params, T, a.n, a.n_class);
@@ -1405,7 +1439,10 @@ static int sample_heads_launch(const t2h_sample_heads_args* args, const t2h_samp
     const dim3 lgrid(a.n_rows * SL_SPLIT), pgrid(a.n_rows);
     hipLaunchKernelGGL((params ? sample_logits_kernel<512, true> : sample_logits_kernel<512, false>), lgrid,
                        dim3(SL_THREADS), 0, s, a, a.logits_ws, params, T);
-    hipLaunchKernelGGL(T2H_TAIL_KERNEL_LOGP(sample_pick_kernel, a.logp, ), pgrid, dim3(SH_THREADS), 0, s, a, a.logits_ws, params, T);
+    if (a.philox_seed_img)
+      hipLaunchKernelGGL(T2H_TAIL_KERNEL_LOGP(sample_pick_kernel, a.logp, true, ), pgrid, dim3(SH_THREADS), 0, s, a, a.logits_ws, params, T);
+    else
+      hipLaunchKernelGGL(T2H_TAIL_KERNEL_LOGP(sample_pick_kernel, a.logp, false, ), pgrid, dim3(SH_THREADS), 0, s, a, a.logits_ws, params, T);
     T2H_CHECK_LAUNCH("t2h_sample_heads");
     return T2H_OK;
   }
@@ -1538,6 +1575,21 @@ extern "C" int t2h_unmask_schedule_keep(uint64_t seed, uint64_t offset, uint32_t
   T2H_REQUIRE(keep != nullptr, "t2h_unmask_schedule_keep: NULL pointer");
   return unmask_schedule_launch("t2h_unmask_schedule_keep", seed, offset, rand_grid_threads, rand_inc, expo_inc, tex, keep,
                                 n, steps, n_heads, step_of_row, head_mask, stream);
+}
+
+extern "C" int t2h_unmask_schedule_batch(const uint64_t* seeds, uint32_t rand_grid_threads, uint32_t rand_inc,
+                                         uint32_t expo_inc, const int64_t* tex, const uint8_t* keep, int32_t B, int32_t T,
+                                         int32_t steps, int32_t n_heads, int32_t* step_of_row, uint32_t* head_mask,
+                                         void* stream) {
+  T2H_REQUIRE(seeds && tex && step_of_row && head_mask, "t2h_unmask_schedule_batch: NULL pointer");
+  T2H_REQUIRE(B > 0 && T > 0 && (int64_t)B * T <= 0x7fffffff && steps >= 1 && steps <= SCHED_MAX_STEPS && n_heads > 0 &&
+                  n_heads <= T2H_MAX_HEADS && rand_grid_threads > 0 && rand_inc % 4 == 0 && expo_inc % 4 == 0,
+              "t2h_unmask_schedule_batch: bad arguments (B=%d T=%d steps=%d n_heads=%d)", B, T, steps, n_heads);
+  hipLaunchKernelGGL((keep ? unmask_schedule_batch_kernel<true> : unmask_schedule_batch_kernel<false>), dim3(B),
+                     dim3(SCHED_THREADS), 0, static_cast<hipStream_t>(stream), seeds, rand_grid_threads, rand_inc, expo_inc,
+                     tex, keep, T, steps, step_of_row, head_mask);
+  T2H_CHECK_LAUNCH("t2h_unmask_schedule_batch");
+  return T2H_OK;
 }
 
 extern "C" int t2h_edit_prefill(const int64_t* src_lists, const int64_t* tex, const uint8_t* keep, int64_t mask_id,

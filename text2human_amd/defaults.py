@@ -172,6 +172,16 @@ def with_refine_sampling(opt, temp=None, top_k=None, top_p=None):
     return opt
 
 
+def with_per_image_seeds(opt, on=True):
+    """`opt` with the key that makes inference draw every image from a stream of its own, seeded from (manual_seed, its
+    img_name) (options.per_image_seeding / options.image_seed; off: the key is removed).  Returns opt."""
+    if on:
+        opt['per_image_seeds'] = True
+    else:
+        opt.pop('per_image_seeds', None)
+    return opt
+
+
 def write_yaml(opt, path):
     with open(path, 'w') as f:
         yaml.safe_dump(dict(opt), f, sort_keys=False)

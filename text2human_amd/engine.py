@@ -7,6 +7,7 @@ time, models/sample_model.py:220; every op is per-sample so batching is exact)
 and keeps activations as NHWC pixel rows [B*H*W, C] / token rows [B*T, C] in
 HBM.  PyTorch only allocates tensors and provides the stream.
 """
+import contextlib
 import gc
 import numbers
 import os
@@ -185,6 +186,14 @@ class _ExactFp32:
     buffers of SamplerNet._buffers hold the operands and how the norm producer, a Linear and attention are called.
     This one: fp32 operands, the exact-fp32 kernels."""
 
+    cfg_rows = 0  # (the split arithmetics, batch-invariant runs: see SamplerNet.invariant_rows)
+    image_rows = 0  # batch-invariant runs: T, the rows of ONE image (attention runs on the form the dispatcher gives B = 1)
+
+    def _one_image_form(self):
+        """None (nothing forced), or in a batch-invariant run the attention form of a single image, asked of the
+        dispatcher itself"""
+        return ops.mha_split_auto_form(1, self.image_rows, self.n_head) if self.image_rows else None
+
     def __init__(self, net, mha=True):
         self.P, self.nm, self.n_head, self.mha = net.P, net.name, net.n_head, mha
 
@@ -225,6 +234,8 @@ class _Fp16Planes(_ExactFp32):
 
     def linear(self, i, lin, a, role, m, N, K, dst, to=None, residual=None, act=ACT_NONE, **fmt):
         p = f'{self.nm}.{i}.{lin}'
+        if self.cfg_rows:  # (without it: today's call, keyword for keyword)
+            fmt = dict(fmt, cfg_rows=self.cfg_rows)
         ops.gemm_split(a, self.P[f'{p}.{self.key}'], m, N, K, out=None if to else dst, out_split=dst if to else None,
                        bias=self.P[f'{p}.b'], residual=residual, act=act, **fmt)
 
@@ -236,7 +247,8 @@ class _Fp16Planes(_ExactFp32):
     def attention(self, i, qk, vt, B, T, C, y):
         if not self.mha:
             return ops.mha_noncausal_split(qk, B, T, self.n_head, y)
-        ops.mha_split(qk, 3 * C, vt, B, T, self.n_head, out_split=y)
+        with ops.mha_split_form(self._one_image_form()):
+            ops.mha_split(qk, 3 * C, vt, B, T, self.n_head, out_split=y)
 
 
 class _X8(_Fp16Planes):
@@ -257,7 +269,8 @@ class _X8(_Fp16Planes):
                        out_x8_scale=self.sa.get((i, to)), **kw)
 
     def attention(self, i, qk, vt, B, T, C, y):
-        ops.mha_split_x8(qk, 3 * C, vt, B, T, self.n_head, y, self.sa[i, 'y'])
+        with ops.mha_split_form(self._one_image_form()):
+            ops.mha_split_x8(qk, 3 * C, vt, B, T, self.n_head, y, self.sa[i, 'y'])
 
 
 class SamplerNet:
@@ -287,6 +300,14 @@ class SamplerNet:
         self._graphs = {}       # captured sampling rounds (RoundGraph), see sample_tokens
         self.last_stats = None  # schedule.stats of the last sample_tokens run
         self.last_launch_mode = None  # 'graph' (one replay per round) / 'eager' (individual launches)
+        # Batch-invariant arithmetic (per-image seeds; set by a seeded sample_tokens for its own run):
+        # T > 0 = a row's bits must be those of the call on its image alone.  What depends on the batch today is only
+        # WHICH kernel form a launch picks: the split GEMMs their tile configuration (by M), attention its form (by B),
+        # the last layer's compacted tail the few-rows kernel or a tile (by the round's row count).  With T set the
+        # Linears of the layers pick the configuration of M = T, attention the form the dispatcher gives one image, and
+        # the tail always runs on the few-rows kernel, compacted or not -- as the unseeded single-image call does while
+        # its rounds list at most 64 rows.
+        self.invariant_rows = 0
 
     def _buffers(self, M, C, dev):
         key = (M, C, str(dev))
@@ -313,6 +334,7 @@ class SamplerNet:
     # GEMM kernel (K split over 8 waves): tolerance-level equality, not bitwise
     # (tests/test_gpu_edge_cases.py compares the tokens of both forms on the bench configuration).
     TRIM_MAX_ROWS = 256
+    FEW_ROWS = 16  # a row count the split GEMM's dispatcher gives the few-rows kernel (M <= 64)
 
     def _arithmetic(self):
         """The arithmetic of this call (looked up per call: a caller may switch `x8` off for one run)."""
@@ -368,6 +390,7 @@ class SamplerNet:
         L = self.desc['n_layers']
         self._deferred = None
         ar = self._arithmetic()
+        ar.cfg_rows = ar.image_rows = int(self.invariant_rows)
         h, qk, vt, y, u = ar.buffers(buf)
         for i in range(L):
             self._attention_half(ar, i, B, T, x, h, qk, vt, y)
@@ -393,7 +416,13 @@ class SamplerNet:
         else:
             m, xc, yc, compact = M, x, ys, False
             hc, uc = buf['h_split'], buf['u_split']
-        self._tail_half(self._arithmetic(), self.desc['n_layers'] - 1, m, xc, yc, hc, uc)
+        ar = self._arithmetic()
+        if self.invariant_rows:
+            # the few-rows kernel whatever the round lists -- also when the list is too long for the compacted buffers
+            # and the tail runs on all evaluated rows: the SAME image lists fewer rows in a smaller batch, and its bits
+            # may not depend on which branch above its batch took (that kernel handles any M, 16 rows per workgroup)
+            ar.cfg_rows = self.FEW_ROWS
+        self._tail_half(ar, self.desc['n_layers'] - 1, m, xc, yc, hc, uc)
         return xc, compact
 
     def ensure_x8(self):
@@ -584,8 +613,12 @@ class SampleSchedule:
     rows[start[r]:start[r + 1]], each with its own noise reference."""
 
     def __init__(self, rows, start, round_steps, noise_kind, seed=None, offsets=None, expo_rows=None, slots=None,
-                 host=None, perm=None, rng_rows=None, active=None, kept=None):
+                 host=None, perm=None, rng_rows=None, active=None, kept=None, seeds=None, seed_offsets=None):
         self.rows, self.start, self.round_steps = rows, start, round_steps
+        # per-image seeds (DESIGN.md 4.6h): seeds = one Python int per image in the SCHEDULE's sample order (the order
+        # the batch has on the device; `seed` is then None), seed_offsets int64 [B] = where every image's private stream
+        # ends, in the caller's order
+        self.seeds, self.seed_offsets = seeds, seed_offsets
         self.kept = kept  # region editing: bool [B*T] (schedule order) of the rows that keep their source token
         self.host = host  # (row order, per-row offsets[, rng rows]) as numpy, for the padded tables of the graph path
         # finished samples leave the batch (schedule.leave_order): perm[new position] = original sample, rows /
@@ -624,25 +657,54 @@ def _texture_ids(tex_tok, n_books):
     return tex_flat, tex_host
 
 
-def build_schedule(tex_tok, sample_steps, n_books, n_class, noise, compact=True, shrink=False, init=None):
+def build_schedule(tex_tok, sample_steps, n_books, n_class, noise, compact=True, shrink=False, init=None, seeds=None):
     """The unmasking schedule + RNG bookkeeping of one sample_fn call (schedule.py), consuming
     `noise` exactly as the reference's loop would (models/sample_model.py:279-306).  shrink (compact rounds on the
     device generator only): the samples are reordered so that finished ones leave the batch (SampleSchedule.perm).
     init = (src_lists int64 [n_books, B*T], keep uint8 [B*T]) (region editing): the kept rows start unmasked and are
-    never drawn; a kept row without a source token raises T2HError before the generator has moved."""
+    never drawn; a kept row without a source token raises T2HError before the generator has moved.
+    seeds (one integer in [0, 2^64) per image): every image gets the schedule, and the generator offsets,
+    of the call on that image alone after manual_seed(seeds[b]) -- t2h_unmask_schedule_batch; `noise` must be the
+    device generator's emulation (it is neither read nor advanced)."""
     return _schedule(*_texture_ids(tex_tok, n_books), tex_tok.shape[0], sample_steps, n_books, n_class, noise, compact,
-                     shrink, init)
+                     shrink, init, seeds)
 
 
-def _schedule(tex_flat, tex_host, B, sample_steps, n_books, n_class, noise, compact, shrink, init):
+def _seeded_noise_check(noise, T, n_class):
+    """Per-image seeds reproduce torch's draws of ONE image in the kernels: there is no explicit form of them"""
+    if not isinstance(noise, TorchDeviceNoise):
+        raise ValueError('seeds: per-image seeds cannot be combined with an explicit noise source')
+    if not noise.emulation_ok(T, n_class):
+        raise _lib.T2HError('seeds: the in-kernel reproduction of torch\'s Philox draws does not match this torch / ROCm '
+                            'build, so the single-image call that defines a seeded image cannot be reproduced')
+
+
+def _schedule(tex_flat, tex_host, B, sample_steps, n_books, n_class, noise, compact, shrink, init, seeds=None):
     """build_schedule on texture ids that were checked already (_texture_ids)"""
     dev, n = tex_flat.device, tex_flat.numel()
     T = n // B
     to_dev = lambda a: torch.from_numpy(a).to(dev)
     keep = err = kept = None
+    if seeds is not None:
+        seeds = options.image_seeds(B, seeds)
+        _seeded_noise_check(noise, T, n_class)
     if init is not None:
         src_lists, keep = init
         err = ops.edit_prefill(src_lists, tex_flat, keep, 0, n_class)  # (check only: the error word)
+    if seeds is not None:
+        # one launch, one workgroup per image; the global generator is neither read nor advanced
+        step_dev, mask_dev, rand_inc, expo_inc = ops.unmask_schedule(None, 0, tex_flat, sample_steps, n_books, n_class,
+                                                                     keep=keep, seeds=seeds)
+        step_of_row = step_dev.cpu().numpy()
+        if init is not None:
+            kept = _init_check(err, keep, T)
+        head_mask = mask_dev.cpu().numpy().astype(np.int64) & 0xFFFFFFFF
+        expo_off, final = schedule.draw_offsets_per_image(head_mask, sample_steps, rand_inc, expo_inc, n_books)
+        p = schedule.plan_rounds(step_of_row, tex_host, B, T, compact, shrink, kept, expo_off, per_image=True)
+        in_order = seeds if p.perm is None else [seeds[int(b)] for b in p.perm]
+        return SampleSchedule(to_dev(p.order.astype(np.int32)), p.start, p.round_steps, 'philox', seed=None,
+                              offsets=to_dev(p.offs), host=(p.order, p.offs, p.rng_rows), perm=p.perm,
+                              rng_rows=to_dev(p.rng_rows), active=p.active, kept=p.kept, seeds=in_order, seed_offsets=final)
     if isinstance(noise, TorchDeviceNoise) and noise.emulation_ok(n, n_class):
         # one launch reproduces every `rand` draw; one host read fetches the whole schedule
         gen, _ = noise.generator()
@@ -725,12 +787,13 @@ def _initial_state(init, tex_tok, n_books, mask_id, n_class, x_t=None, out=None)
 
 
 def _round(net, x_t, out, segm_tok, tex_tok, rows, n_rows, noise, temp, logits_ws, trunc_kw, defer=True, active=None,
-           logp=None, targets=None, rank=None):
+           logp=None, targets=None, rank=None, seed_img=None):
     """One round of the reference's loop: the transformer on x_t (defer: the last layer's tail on the listed rows only,
     and only the first `active` samples), then the tokens of the first n_rows of `rows` drawn into x_t / out.  temp /
     trunc_kw: the scalar controls (_trunc_kw), or temp None and the per-image table (_per_image_kw).  logp (f32 [B*T],
     None = off): the drawn rows' log-probabilities (ops.sample_heads).  targets (int64 [n_books, B*T], None = off; needs
-    logp): scoring -- the listed rows take their token from it instead of drawing one; rank (int32 [B*T], optional)."""
+    logp): scoring -- the listed rows take their token from it instead of drawing one; rank (int32 [B*T], optional).
+    seed_img (int64 [B], None = off): per-image seeds, in the order the batch has here."""
     compact = False
     if defer:
         net.hidden(x_t, segm_tok, tex_tok, defer_tail=True, active=active)
@@ -741,6 +804,8 @@ def _round(net, x_t, out, segm_tok, tex_tok, rows, n_rows, noise, temp, logits_w
         trunc_kw = dict(trunc_kw, logp=logp)
     if targets is not None:
         trunc_kw = dict(trunc_kw, targets=targets, rank=rank)
+    if seed_img is not None:
+        trunc_kw = dict(trunc_kw, seed_img=seed_img, img_rows=int(tex_tok.shape[1]))
     ops.sample_heads(hidden, *net.final_norm_and_heads(), {}, rows, n_rows, tex_tok.view(-1), temp, x_t, out,
                      row_noise=noise, hidden_compact=compact, logits_ws=logits_ws, **trunc_kw)
 
@@ -755,7 +820,7 @@ class RoundGraph:
     (prepare), replayed for every round of every run."""
 
     def __init__(self, net, B, T, steps, maxr, n_books, n_class, temp, mask_id, dev, trunc=(0, 0), per_image=False,
-                 logp=False, score=None):
+                 logp=False, score=None, seeded=False):
         i64 = lambda *s: torch.empty(s, dtype=torch.int64, device=dev)
         i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)
         # (a weak reference: net._graphs owns this object -- a strong one would make a cycle that only the cyclic
@@ -774,6 +839,10 @@ class RoundGraph:
         self.rows_tbl, self.offs_tbl, self.rng_tbl = i32(steps, maxr), i64(steps, maxr), i32(steps, maxr)
         self.cur_rows, self.cur_offs, self.cur_rng = i32(maxr), i64(maxr), i32(maxr)
         self.round_ctr, self.seed = i32(1), i64(1)
+        # per-image seeds: a persistent buffer the captured tail points to, refreshed by run() like the per-image table
+        # (the schedule's sample order) -- its VALUES are not captured: runs with other seeds replay the same graphs
+        self.seed_img = i64(B) if seeded else None
+        self.captures = 0  # rounds captured so far (a run that finds all its graphs adds none)
         self.logits_ws = torch.empty((maxr, n_class), dtype=torch.float32, device=dev)
         # per-token log-probabilities (return_logp): a persistent buffer the captured tail points to, NaN-filled by run()
         # beside the initial state; None = the tail without them (part of the graph key)
@@ -795,7 +864,7 @@ class RoundGraph:
         sizes every lazily allocated workspace); a capture itself executes nothing.  Call on self.stream."""
         _initial_state(None, self.tex, self.out.shape[0], self.mask_id, self.n_class, self.x_t, self.out)
         for t in (self.segm, self.tex, self.rows_tbl, self.offs_tbl, self.rng_tbl, self.round_ctr, self.seed,
-                  self.targets):
+                  self.targets, self.seed_img):
             if t is not None:
                 t.zero_()
         self.body(self.B)
@@ -810,7 +879,7 @@ class RoundGraph:
                              self.cur_rng, self.maxr)
         _round(self._net(), self.x_t, self.out, self.segm, self.tex, self.cur_rows, self.maxr,
                ('philox', self.seed, self.cur_offs, self.cur_rng), self.temp, self.logits_ws, self.trunc, active=k,
-               logp=self.logp, targets=self.targets, rank=self.rank)
+               logp=self.logp, targets=self.targets, rank=self.rank, seed_img=self.seed_img)
 
     def capture(self, k):
         g = torch.cuda.CUDAGraph()
@@ -826,6 +895,7 @@ class RoundGraph:
             if gc_was_on:
                 gc.enable()
         self.graphs[k] = g
+        self.captures += 1
 
     def run(self, sched, segm_tok, tex_tok, init=None, params=None, targets=None):
         """All rounds of one run on this graph's stream; returns `out` (valid once the caller's stream
@@ -860,7 +930,10 @@ class RoundGraph:
             if self.rank is not None:
                 self.rank.fill_(-1)
             self.round_ctr.zero_()
-            self.seed.fill_(schedule.as_int64(sched.seed))  # (a uint64 seed >= 2^63 in its two's-complement form)
+            if self.seed_img is not None:
+                self.seed_img.copy_(ops.seeds_tensor(sched.seeds, 'cpu'), non_blocking=False)
+            else:
+                self.seed.fill_(schedule.as_int64(sched.seed))  # (a uint64 seed >= 2^63 in its two's-complement form)
             for r in range(R):
                 k = int(active[r])
                 self.graphs[k].replay()
@@ -884,27 +957,28 @@ def _per_image_kw(params, T):
 SCORE, SCORE_RANK = 'score', 'score+rank'  # the trailing key element of a scoring graph: without / with the rank output
 
 
-def round_graph_key_per_image(B, T, sample_steps, maxr, mask_id, n_books, x8, logp=False, score=None):
+def round_graph_key_per_image(B, T, sample_steps, maxr, mask_id, n_books, x8, logp=False, score=None, seeded=False):
     """The key of the captured rounds of per-image runs: the table is read from a buffer of the graph, so neither
     temperatures nor truncation settings are held by value -- runs with different values share the captures.  logp
     (the tail that also writes log-probabilities): one more trailing element, absent without it.  score (SCORE /
     SCORE_RANK: the tail that reads its tokens from a target map, score_tokens): likewise."""
     return ((B, T, sample_steps, maxr, int(mask_id), n_books, bool(x8), 'per-sample') + (('logp', ) if logp else ()) +
-            ((score, ) if score else ()))
+            ((score, ) if score else ()) + (('seeded', ) if seeded else ()))
 
 
-def round_graph_key(B, T, sample_steps, maxr, temp, mask_id, n_books, x8, trunc=(0, 0), logp=False, score=None):
+def round_graph_key(B, T, sample_steps, maxr, temp, mask_id, n_books, x8, trunc=(0, 0), logp=False, score=None,
+                    seeded=False):
     """What a captured round (RoundGraph) holds BY VALUE: two calls share a graph iff this key is equal.  logp (the tail
     that also writes log-probabilities): one more trailing element, absent without it -- the keys, and so the captures,
     of runs without it are what they always were.  score (SCORE / SCORE_RANK: the scoring tail, score_tokens): one more
     trailing element by the same rule."""
     return ((B, T, sample_steps, maxr, float(temp), int(mask_id), n_books, bool(x8), int(trunc[0]), int(trunc[1])) +
-            (('logp', ) if logp else ()) + ((score, ) if score else ()))
+            (('logp', ) if logp else ()) + ((score, ) if score else ()) + (('seeded', ) if seeded else ()))
 
 
 def sample_tokens(net, segm_tok, tex_tok, sample_steps, mask_id, temp=1.0, noise=None,
                   n_books=18, step_hook=None, round_hook=None, compact=None, init=None, top_k=None, top_p=None,
-                  return_logp=False):
+                  return_logp=False, seeds=None):
     """BaseSampleModel.sample_fn (models/sample_model.py:256-328) on device.
 
     The unmasking schedule and every generator offset are computed up front (build_schedule: they
@@ -935,11 +1009,29 @@ def sample_tokens(net, segm_tok, tex_tok, sample_steps, mask_id, temp=1.0, noise
     changes the token, never the distribution); NaN for rows that were never drawn (kept by a region edit).  Tokens and
     generator are those of the call without it.
 
+    seeds (one integer in [0, 2^64) per image, the caller's sample order): image b is what this function
+    returns for a batch that holds image b alone after torch.cuda.manual_seed(seeds[b]) -- its own schedule, its own
+    generator offsets, its own noise -- whatever else is in the batch.  The global generator is neither read nor
+    advanced; net.last_seed_offsets (int64 [B], numpy) = where every image's private stream ends.  Not with an explicit
+    `noise` (ValueError); T2HError where the kernels cannot reproduce this torch build's draws.
+
     Test hooks, called after each round and allowed to overwrite x_t in place (teacher forcing):
     round_hook(r, steps, x_t, out) with steps[b] = the step sample b just took (0 = idle);
     step_hook(t, x_t, out) (compact=False only; steps that change no token are skipped)."""
-    return _token_loop(net, segm_tok, tex_tok, sample_steps, mask_id, temp, noise, n_books, step_hook, round_hook, compact,
-                       init, top_k, top_p, return_logp)
+    with _invariant(net, segm_tok.shape[1] if seeds is not None else 0):
+        return _token_loop(net, segm_tok, tex_tok, sample_steps, mask_id, temp, noise, n_books, step_hook, round_hook,
+                           compact, init, top_k, top_p, return_logp, seeds=seeds)
+
+
+@contextlib.contextmanager
+def _invariant(net, rows):
+    """a seeded run: every launch picks its kernel form as the call on one image of `rows` token rows does
+    (SamplerNet.invariant_rows); rows = 0: nothing changes"""
+    net.invariant_rows = int(rows)
+    try:
+        yield
+    finally:
+        net.invariant_rows = 0
 
 
 def _target_check(targets, tex_flat, n_class, T):
@@ -971,17 +1063,35 @@ def score_tokens(net, segm_tok, tex_tok, sample_steps, mask_id, targets, temp=1.
     Every row's own-texture target must lie in [0, n_class): T2HError (first offending (sample, row)) before the
     generator has moved.  The generator is consumed exactly as sample_tokens with the same init consumes it, the
     offsets of the exponential draws that are never made included: a map that sample_tokens(return_logp=True) drew at
-    generator state G, scored at state G, returns that call's logp bits."""
+    generator state G, scored at state G, returns that call's logp bits.  (Per-image seeds: score_tokens_seeded.)"""
+    return _score_tokens(net, segm_tok, tex_tok, sample_steps, mask_id, targets, temp, noise, n_books, keep, compact,
+                         round_hook, return_rank, None)
+
+
+def score_tokens_seeded(net, segm_tok, tex_tok, sample_steps, mask_id, targets, seeds, temp=1.0, n_books=18, keep=None,
+                        compact=None, return_rank=False):
+    """score_tokens with per-image seeds (seeds as in sample_tokens): every image is scored along the
+    schedule of its own seed, so a map drawn with sample_tokens(seeds=s, return_logp=True) scored with seeds=s returns
+    that call's logp bits, whatever batch either call ran in; the global generator is not touched.  (A function of its
+    own: score_tokens keeps its parameter list.)"""
+    return _score_tokens(net, segm_tok, tex_tok, sample_steps, mask_id, targets, temp, None, n_books, keep, compact, None,
+                         return_rank, options.image_seeds(segm_tok.shape[0], seeds))
+
+
+def _score_tokens(net, segm_tok, tex_tok, sample_steps, mask_id, targets, temp, noise, n_books, keep, compact, round_hook,
+                  return_rank, seeds):
+    """score_tokens / score_tokens_seeded"""
     if tuple(targets.shape) != (n_books, segm_tok.numel()) or targets.dtype != torch.int64:
         raise ValueError(f'targets: int64 [{n_books}, {segm_tok.numel()}] expected, got {targets.dtype} {tuple(targets.shape)}')
     targets = targets.contiguous()
-    return _token_loop(net, segm_tok, tex_tok, sample_steps, mask_id, temp, noise, n_books, None, round_hook, compact,
-                       None if keep is None else (targets, keep), None, None, True,
-                       score=(targets, SCORE_RANK if return_rank else SCORE))
+    with _invariant(net, segm_tok.shape[1] if seeds is not None else 0):
+        return _token_loop(net, segm_tok, tex_tok, sample_steps, mask_id, temp, noise, n_books, None, round_hook, compact,
+                           None if keep is None else (targets, keep), None, None, True,
+                           score=(targets, SCORE_RANK if return_rank else SCORE), seeds=seeds)
 
 
 def _token_loop(net, segm_tok, tex_tok, sample_steps, mask_id, temp, noise, n_books, step_hook, round_hook, compact, init,
-                top_k, top_p, return_logp, score=None):
+                top_k, top_p, return_logp, score=None, seeds=None):
     """The loop of sample_tokens (see there).  score = (targets, SCORE or SCORE_RANK): score_tokens -- every round's
     tail reads its tokens from `targets`; returns logp, or (logp, rank)."""
     B, T = segm_tok.shape
@@ -990,6 +1100,10 @@ def _token_loop(net, segm_tok, tex_tok, sample_steps, mask_id, temp, noise, n_bo
         compact = step_hook is None and os.environ.get('T2H_COMPACT_ROUNDS', '1') != '0'
     if compact and step_hook is not None:
         raise ValueError('step_hook needs compact=False (samples are at different steps in a compact round)')
+    if seeds is not None:  # (raises before anything is evaluated or drawn)
+        seeds = options.image_seeds(B, seeds)
+        if noise is not None and not isinstance(noise, TorchDeviceNoise):
+            raise ValueError('seeds: per-image seeds cannot be combined with an explicit noise source')
     noise, n_class, sp, tex_flat, tex_host = _begin_run(net, tex_tok, n_books, noise, init, temp, top_k, top_p)
     table = sp.table
     targets = score_kind = None
@@ -998,7 +1112,8 @@ def _token_loop(net, segm_tok, tex_tok, sample_steps, mask_id, temp, noise, n_bo
         _target_check(targets, tex_flat, n_class, T)
     # finished samples leave the batch (T2H_SHRINK_BATCH=0 opts out; hooks see the batch in its own order)
     shrink = (compact and step_hook is None and round_hook is None and os.environ.get('T2H_SHRINK_BATCH', '1') != '0')
-    sched = _schedule(tex_flat, tex_host, B, sample_steps, n_books, n_class, noise, compact, shrink, init)
+    sched = _schedule(tex_flat, tex_host, B, sample_steps, n_books, n_class, noise, compact, shrink, init, seeds)
+    net.last_seed_offsets = sched.seed_offsets
     defer = bool(net.split and net.split_mha and os.environ.get('T2H_TRIM_LAST_LAYER', '1') != '0')
     # (only the deferred-tail form of hidden() runs on the prefix of running samples; every other form evaluates the
     # whole batch each round, and the counts say so)
@@ -1031,13 +1146,15 @@ def _token_loop(net, segm_tok, tex_tok, sample_steps, mask_id, temp, noise, n_bo
         net._buffers(n, net.desc['C'], dev)  # (a change of batch size drops the graphs of the old buffers)
         if table is None:
             key = round_graph_key(B, T, sample_steps, maxr, temp, mask_id, n_books, net.x8, sp.trunc,
-                                  logp=return_logp and score is None, score=score_kind)
+                                  logp=return_logp and score is None, score=score_kind, seeded=seeds is not None)
         else:
             key = round_graph_key_per_image(B, T, sample_steps, maxr, mask_id, n_books, net.x8,
-                                            logp=return_logp and score is None, score=score_kind)
+                                            logp=return_logp and score is None, score=score_kind,
+                                            seeded=seeds is not None)
         if key not in net._graphs:
             net._graphs[key] = RoundGraph(net, B, T, sample_steps, maxr, n_books, n_class, temp, mask_id, dev,
-                                          trunc=sp.trunc, per_image=table is not None, logp=return_logp, score=score_kind)
+                                          trunc=sp.trunc, per_image=table is not None, logp=return_logp, score=score_kind,
+                                          seeded=seeds is not None)
         graph = net._graphs[key]
         out = in_batch_order(graph.run(sched, segm_tok, tex_tok, init=init, params=table, targets=targets).clone())
         if score is not None:
@@ -1049,11 +1166,12 @@ def _token_loop(net, segm_tok, tex_tok, sample_steps, mask_id, temp, noise, n_bo
     logp = torch.full((n, ), float('nan'), dtype=torch.float32, device=dev) if return_logp else None
     rank = torch.full((n, ), -1, dtype=torch.int32, device=dev) if score_kind == SCORE_RANK else None
     logits_ws = torch.empty((max(sched.max_rows, 1), n_class), dtype=torch.float32, device=dev)
+    seed_img = ops.seeds_tensor(sched.seeds, dev) if sched.seeds is not None else None
     for r in range(sched.n_rounds):
         lo, hi = int(sched.start[r]), int(sched.start[r + 1])
         k = int(sched.active[r]) if sched.active is not None else None
         _round(net, x_t, out, segm_tok, tex_tok, sched.rows[lo:hi], hi - lo, sched.row_noise(lo, hi), sp.temp, logits_ws,
-               tail_kw, defer, k, logp, targets, rank)
+               tail_kw, defer, k, logp, targets, rank, seed_img)
         if round_hook is not None:
             round_hook(r, sched.round_steps[r], x_t, out)
         if step_hook is not None:

@@ -114,22 +114,31 @@ class BaseSampleModel():
 
     # ------------------------------------------------------------ stage S
     @torch.no_grad()
-    def sample_fn(self, temp=1.0, sample_steps=None, top_k=None, top_p=None, return_logp=False):
+    def sample_fn(self, temp=1.0, sample_steps=None, top_k=None, top_p=None, return_logp=False, seeds=None):
         """models/sample_model.py:256-328 -> list of 18 int64 [B, 512].  top_k / top_p (not in the reference; DESIGN.md
         "Truncated sampling"): every draw only among the k most likely classes / the smallest set of most likely classes
         holding top_p of the probability.  None = off = the reference's draw.  temp / top_k / top_p may each be a
         sequence with one entry per image of the batch (DESIGN.md "Per-image sampling controls"): image b is then the
         image b of the call with its own values as scalars.  return_logp: -> (lists, logp), logp float32 [B, 512] = the
         log-probability of every drawn token under the full softmax of logits / temp when it was drawn (DESIGN.md 4.6f;
-        NaN: never drawn); tokens and generator are those of the call without it."""
-        return self._sample(temp, sample_steps or self.sample_steps, top_k=top_k, top_p=top_p, return_logp=return_logp)
+        NaN: never drawn); tokens and generator are those of the call without it.
+        seeds (opt-in): one integer in [0, 2^64) per image -- image b is then what this method returns
+        for a batch that holds image b alone after torch.cuda.manual_seed(seeds[b]), with the same temp / top_k / top_p /
+        sample_steps: a function of (checkpoint, its own input, its own seed), not of the batch.  The global generator
+        is neither read nor advanced; self.last_seed_offsets (int64 [B]) = the generator offset each of those
+        single-image calls would end at."""
+        return self._sample(temp, sample_steps or self.sample_steps, top_k=top_k, top_p=top_p, return_logp=return_logp,
+                            seeds=seeds)
 
     @torch.no_grad()
-    def sample_fn_confidence(self, rounds=16, temp=1.0, choice_temp=4.5, top_k=None, top_p=None, return_logp=False):
+    def sample_fn_confidence(self, rounds=16, temp=1.0, choice_temp=4.5, top_k=None, top_p=None, return_logp=False,
+                             seeds=None):
         """Confidence-ordered parallel decoding (opt-in; DESIGN.md "Confidence-ordered decoding"): all tokens in
         `rounds` transformer evaluations instead of one per active step -> list of 18 int64 [B, 512] like sample_fn.
         rounds / choice_temp / temp / top_k / top_p may each be a sequence with one entry per image.  return_logp: as in
-        sample_fn (the confidence of every committed token, from the round that committed it)."""
+        sample_fn (the confidence of every committed token, from the round that committed it).  seeds: not supported on
+        this path yet (ValueError, nothing drawn)."""
+        self._no_seeds(seeds, 'sample_fn_confidence')
         return self._sample(temp, None, confidence=self._confidence_args(rounds, choice_temp), top_k=top_k, top_p=top_p,
                             return_logp=return_logp)
 
@@ -147,14 +156,27 @@ class BaseSampleModel():
         """(top_k, top_p) of the options `sample_top_k` / `sample_top_p` (None, None: off)."""
         return options.sampling_truncation(self.opt)
 
+    @staticmethod
+    def _no_seeds(seeds, what):
+        """the paths whose draws still come from the shared generator stream refuse per-image seeds"""
+        if seeds is not None:
+            raise ValueError(f'{what}: per-image seeds are not supported on this path (its draws use the shared generator '
+                             'stream); use sample_fn / resample_fn(order=\'random\') / score_fn')
+
     def _sample(self, temp, sample_steps, init=None, confidence=None, top_k=None, top_p=None, return_logp=False,
-                score=None):
+                score=None, seeds=None):
         """sample_fn's body (init: engine.sample_tokens' initial state of a region edit; confidence = (rounds,
         choice_temp): engine.sample_tokens_confidence instead of the reference's loop; top_k / top_p: truncated
         sampling, passed to every attempt of the fall-back chain below; return_logp: -> (lists, logp [B, 512]), the
         log-probabilities of the attempt that produced the tokens; score = (targets [18, B*512], keep or None,
-        return_rank): engine.score_tokens on that map instead of a draw -> logp [B, 512], or (logp, rank))."""
+        return_rank): engine.score_tokens on that map instead of a draw -> logp [B, 512], or (logp, rank)).  seeds: per-image
+        seeds of sample_tokens / score_tokens; every attempt of the fall-back chain runs with the same ones."""
         logp_kw = dict(return_logp=True) if return_logp else {}  # (without it: today's calls, keyword for keyword)
+        seed_kw = {}
+        if seeds is not None:
+            seed_kw = dict(seeds=options.image_seeds(self.batch_size, seeds))  # (raises before anything is drawn)
+            if self.noise is not None and not isinstance(self.noise, engine.TorchDeviceNoise):
+                raise ValueError('seeds: per-image seeds cannot be combined with an explicit noise source')
         ops.sampling_params(self.batch_size, temp, top_k, top_p)  # (raises before anything is evaluated or drawn)
         tex_tok = self._texture_tokens(self.texture_mask)
         # The reference computes ANY checkpoint in fp32 (transformer_arch.py:91-99).  The split-precision kernels
@@ -168,7 +190,11 @@ class BaseSampleModel():
         try:
             for _ in range(3):  # x8 planes -> fp16 planes -> exact fp32, each at most once
                 try:
-                    if score is not None:
+                    if score is not None and seeds is not None:
+                        out = engine.score_tokens_seeded(net, self.segm_tokens.contiguous(), tex_tok, sample_steps,
+                                                         self.mask_id, score[0], seed_kw['seeds'], temp=temp, keep=score[1],
+                                                         return_rank=score[2])
+                    elif score is not None:
                         out = engine.score_tokens(net, self.segm_tokens.contiguous(), tex_tok, sample_steps, self.mask_id,
                                                   score[0], temp=temp, noise=self.noise, keep=score[1],
                                                   return_rank=score[2])
@@ -180,7 +206,7 @@ class BaseSampleModel():
                     else:
                         out = engine.sample_tokens(net, self.segm_tokens.contiguous(), tex_tok, sample_steps,
                                                    self.mask_id, temp=temp, noise=self.noise, init=init,
-                                                   top_k=top_k, top_p=top_p, **logp_kw)
+                                                   top_k=top_k, top_p=top_p, **logp_kw, **seed_kw)
                     break
                 except engine.X8RangeError as e:
                     # an activation beyond 14x its calibration maximum: the 8-bit planes saturated, the fp16 planes are
@@ -197,6 +223,8 @@ class BaseSampleModel():
                     net = self._exact_sampler()
         finally:
             self.sampler_fn.x8 = x8_was
+        offs = getattr(net, 'last_seed_offsets', None) if seeds is not None else None
+        self.last_seed_offsets = None if offs is None else torch.from_numpy(np.asarray(offs, dtype=np.int64).copy())
         b = self.batch_size
         if score is not None:
             return (out[0].view(b, -1), out[1].view(b, -1)) if score[2] else out.view(b, -1)
@@ -216,6 +244,7 @@ class BaseSampleModel():
         18 x int64 [B, 512] and float32 [B, 512] of the kept candidates, score float32 [B], choice int64 [B].  n = 1 is
         the plain call.  The selection runs on the device; nothing is read back."""
         n = options.best_of_value(n)
+        self._no_seeds(sampling_kwargs.get('seeds'), 'sample_best_of')
         if order is None:
             order = 'confidence' if self._confidence_options() is not None else 'random'
             if order == 'confidence' and 'rounds' not in sampling_kwargs and 'choice_temp' not in sampling_kwargs:
@@ -284,7 +313,7 @@ class BaseSampleModel():
 
     @torch.no_grad()
     def resample_fn(self, top_indices_list, keep, temp=1.0, sample_steps=None, order='random', rounds=None,
-                    choice_temp=4.5, top_k=None, top_p=None, return_logp=False):
+                    choice_temp=4.5, top_k=None, top_p=None, return_logp=False, seeds=None):
         """sample_fn started from `top_indices_list` (18 x int64 [B, 512], e.g. an earlier sample_fn result or a photo's
         top_encode indices) with the rows where keep [B, 512] is nonzero kept.  -> list of 18 int64 [B, 512] in
         sample_fn's format.  A kept row must have an index under the CURRENT texture map (T2HError otherwise; nothing
@@ -292,15 +321,18 @@ class BaseSampleModel():
         16) rounds, every sample on the schedule of its own number of resampled rows.  top_k / top_p: truncated
         sampling of the resampled rows, as in sample_fn.  temp / top_k / top_p / rounds / choice_temp may each be a
         sequence with one entry per image, as in sample_fn / sample_fn_confidence.  return_logp: -> (lists, logp) as in
-        sample_fn; the kept rows are NaN."""
+        sample_fn; the kept rows are NaN.  seeds (order='random' only; as in sample_fn): image b is the single-image
+        resample_fn call on image b after manual_seed(seeds[b])."""
         if order not in ('random', 'confidence'):
             raise ValueError(f"order must be 'random' or 'confidence', got {order!r}")
+        if order == 'confidence':
+            self._no_seeds(seeds, "resample_fn(order='confidence')")
         init = (self._token_lists(top_indices_list, 'resample_fn'), self._keep_rows(keep))
         if not options.is_per_image(rounds):
             rounds = int(rounds or 16)
         confidence = self._confidence_args(rounds, choice_temp) if order == 'confidence' else None
         return self._sample(temp, sample_steps or self.sample_steps, init=init, confidence=confidence, top_k=top_k,
-                            top_p=top_p, return_logp=return_logp)
+                            top_p=top_p, return_logp=return_logp, seeds=seeds)
 
     @torch.no_grad()
     def score_fn(self, top_indices_list, keep=None, temp=1.0, sample_steps=None, return_rank=False, summary=False):
@@ -316,7 +348,21 @@ class BaseSampleModel():
         return_rank: also rank int32 [B, 512] = the number of classes the model held strictly more likely (0 = its
         mode).  summary: also the per-image (sum, count, min) of the scored rows (t2h_logp_summary).  Returns logp, or
         the tuple (logp[, rank][, (sum, count, min)]).  Every row's token under the current texture map must be a class
-        index: T2HError naming the first offending (sample, row), nothing drawn."""
+        index: T2HError naming the first offending (sample, row), nothing drawn.  (Per-image seeds: score_fn_seeded.)"""
+        return self._score(top_indices_list, keep, temp, sample_steps, return_rank, summary, None)
+
+    @torch.no_grad()
+    def score_fn_seeded(self, top_indices_list, seeds, keep=None, temp=1.0, sample_steps=None, return_rank=False,
+                        summary=False):
+        """score_fn with per-image seeds (opt-in; seeds as in sample_fn): every image is scored along the
+        schedule of its own seed -- a map drawn by sample_fn(seeds=s, return_logp=True) scored with seeds=s returns that
+        call's logp bits, whatever batch either call ran in; the global generator is not touched.  Everything else is
+        score_fn.  (A method of its own: score_fn keeps its parameter list.)"""
+        return self._score(top_indices_list, keep, temp, sample_steps, return_rank, summary,
+                           options.image_seeds(self.batch_size, seeds))
+
+    def _score(self, top_indices_list, keep, temp, sample_steps, return_rank, summary, seeds):
+        """score_fn / score_fn_seeded"""
         # (everything below raises before anything is evaluated or drawn)
         if not options.is_per_image(temp) and (isinstance(temp, bool) or not isinstance(temp, numbers.Real) or
                                                not 0.0 < float(temp) < float('inf')):
@@ -324,7 +370,7 @@ class BaseSampleModel():
         ops.sampling_params(self.batch_size, temp)  # (a per-image sequence: its length and every entry)
         targets = self._token_lists(top_indices_list, 'score_fn')
         keep = None if keep is None else self._keep_rows(keep)
-        out = self._sample(temp, sample_steps or self.sample_steps, score=(targets, keep, bool(return_rank)))
+        out = self._sample(temp, sample_steps or self.sample_steps, score=(targets, keep, bool(return_rank)), seeds=seeds)
         res = list(out) if return_rank else [out]
         if summary:
             res.append(ops.logp_summary(res[0].contiguous()))
@@ -537,10 +583,14 @@ class BaseSampleModel():
         return img, u8
 
     @torch.no_grad()
-    def sample_and_refine(self, save_dir=None, img_name=None):
+    def sample_and_refine(self, save_dir=None, img_name=None, seeds=None):
         """models/sample_model.py:215-254.  With both arguments None returns the
         first sample as f32 [1,3,512,256] in [0,1] (what ui_demo.py:162 uses);
-        otherwise writes {save_dir}/{img_name[i]} PNGs."""
+        otherwise writes {save_dir}/{img_name[i]} PNGs.  seeds (options: per_image_seeds, derived by inference();
+        DESIGN.md 4.6h): the top indices of image b are sample_fn's with seeds[b]."""
+        if seeds is not None:
+            seeds = options.image_seeds(self.batch_size, seeds)
+            options.per_image_seeding(dict(self.opt, per_image_seeds=True))  # (the options that cannot keep the promise)
         confidence = self._confidence_options()
         top_k, top_p = self._truncation_options()  # (options: sample_top_k / sample_top_p)
         trunc = {k: v for k, v in (('top_k', top_k), ('top_p', top_p)) if v is not None}
@@ -559,8 +609,9 @@ class BaseSampleModel():
         elif confidence is not None:  # (options: sample_order: confidence)
             sampled_top_indices_list = self.sample_fn_confidence(rounds=confidence[0], temp=1, choice_temp=confidence[1],
                                                                  **trunc)
-        elif trunc:
-            sampled_top_indices_list = self.sample_fn(temp=1, sample_steps=self.sample_steps, **trunc)
+        elif trunc or seeds is not None:
+            seed_kw = dict(seeds=seeds) if seeds is not None else {}
+            sampled_top_indices_list = self.sample_fn(temp=1, sample_steps=self.sample_steps, **trunc, **seed_kw)
         else:
             sampled_top_indices_list = self.sample_fn(temp=1, sample_steps=self.sample_steps)
         want_files = not (save_dir is None and img_name is None)
@@ -576,11 +627,19 @@ class BaseSampleModel():
         _, u8 = self.decode_indices(sampled_top_indices_list, want_u8=True, **refine_kw)
         save_u8_images(u8, save_dir, img_name)
 
+    def _image_seeds(self, img_name):
+        """{} or dict(seeds=...): with the option `per_image_seeds`, options.image_seed of (manual_seed, name) per image"""
+        if not options.per_image_seeding(self.opt):
+            return {}
+        if self.opt['manual_seed'] is None:
+            raise ValueError('per_image_seeds derives every image\'s seed from manual_seed: set it')
+        return dict(seeds=[options.image_seed(self.opt['manual_seed'], name) for name in img_name])
+
     def inference(self, data_loader, save_dir):
         for _, data in enumerate(data_loader):
             img_name = data['img_name']
             self.feed_data(data)
-            self.sample_and_refine(save_dir, img_name)
+            self.sample_and_refine(save_dir, img_name, **self._image_seeds(img_name))
 
 
 _warned = set()
@@ -656,7 +715,7 @@ class SampleFromPoseModel(BaseSampleModel):
             self.generate_parsing_map()
             self.generate_quantized_segm()
             self.generate_texture_map()
-            self.sample_and_refine(save_dir, img_name)
+            self.sample_and_refine(save_dir, img_name, **self._image_seeds(img_name))
 
     def _attr_embedding(self, shape_attr):
         """ShapeAttrEmbedding.forward (shape_attr_embedding_arch.py:23-35)."""

@@ -12,7 +12,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, options
+from . import _lib, options, schedule
 from ._lib import GemmArgs, check
 
 ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2
@@ -532,6 +532,30 @@ def layernorm_x8(x, gamma, beta, out_x8, scale, eps=1e-5):
     return out_x8
 
 
+def mha_split_auto_form(B, T, n_head):
+    """the form (1 all keys / 2 key halves) mha_split / mha_split_x8 pick by themselves for B samples (t2h_mha_split_form)"""
+    form = _lib.load().t2h_mha_split_form(int(B), int(T), int(n_head))
+    if form not in (1, 2):
+        check(1, 't2h_mha_split_form')
+    return form
+
+
+class mha_split_form:
+    """`with mha_split_form(2):` -- mha_split / mha_split_x8 of this thread run on that form (1 all keys, 2 key halves)
+    instead of the one picked from the batch size (t2h_mha_split_force_form); None: nothing is forced."""
+
+    def __init__(self, form):
+        self.form = form
+
+    def __enter__(self):
+        if self.form is not None:
+            self.old = _lib.load().t2h_mha_split_force_form(int(self.form))
+
+    def __exit__(self, *exc):
+        if self.form is not None:
+            _lib.load().t2h_mha_split_force_form(self.old)
+
+
 def mha_split_x8(qk_split, ld_cols, vt, B, T, n_head, out_x8, scale):
     """mha_split with the output written in the x8 format."""
     scale = _chk_x8_scale(scale, 'mha_split_x8')
@@ -541,16 +565,19 @@ def mha_split_x8(qk_split, ld_cols, vt, B, T, n_head, out_x8, scale):
 
 
 def gemm_split(a_split, w_split, M, N, K, out=None, out_split=None, bias=None, residual=None, act=ACT_NONE,
-               vt=None, vt_col0=0, vt_T=0, vt_hd=64, x8=None, out_x8_scale=None, ksplit=0):
+               vt=None, vt_col0=0, vt_T=0, vt_hd=64, x8=None, out_x8_scale=None, ksplit=0, cfg_rows=0):
     """C = act(A @ W^T + bias) + residual on the fp16 matrix cores at fp32-class
     accuracy; a_split / w_split are split rows.  Writes fp32 `out` and / or the
     split-row form `out_split` of the result.  With `vt` the output columns from
     `vt_col0` on go to the transposed value planes of mha_split instead
     (t2h_gemm_split_args.Vt).
     x8 = (scale_A, scale_B): the operands are x8 rows (fp16 plane + two e4m3 planes scaled by those powers of two),
-    the cross terms run on the 8-bit matrix instruction; out_x8_scale: `out_split` is written in the x8 format."""
+    the cross terms run on the 8-bit matrix instruction; out_x8_scale: `out_split` is written in the x8 format.
+    cfg_rows > 0: the tile configuration of a problem of that many rows (t2h_gemm_split_args.cfg_rows) -- a row's bits
+    then do not depend on M."""
     _chk_f32(out, bias, residual)
     g = _lib.GemmSplitArgs()
+    g.cfg_rows = int(cfg_rows)
     if x8 is not None:
         g.fmt = 1
         g.lo_mul = 1.0 / (SPLIT_LO_SCALE * float(x8[0]) * float(x8[1]))
@@ -775,14 +802,41 @@ def philox_uniform(seed, offset, numel, device):
     return out
 
 
-def unmask_schedule(seed, offset, tex, steps, n_heads, n_class, keep=None):
+def seeds_tensor(seeds, device):
+    """validated per-image seeds (options.image_seeds: Python ints in [0, 2^64)) -> int64 [B] on the device holding the
+    same bits (the kernels read the words back as uint64)"""
+    return torch.tensor([schedule.as_int64(s) for s in seeds], dtype=torch.int64).to(device)
+
+
+def unmask_schedule(seed, offset, tex, steps, n_heads, n_class, keep=None, seeds=None):
     """The whole unmasking schedule of a sampling run on torch's device generator (seed, offset before
     the first draw) in one launch (t2h_unmask_schedule).  tex int64 [n]; keep uint8 [n] (region editing,
     t2h_unmask_schedule_keep): rows that start unmasked (step 0, never drawn).  Returns
-    (step_of_row int32 [n], head_mask int32 [steps + 1], rand_inc, expo_inc) -- device tensors."""
+    (step_of_row int32 [n], head_mask int32 [steps + 1], rand_inc, expo_inc) -- device tensors.
+    seeds (per-image seeds; `seed` / `offset` are then not read): one integer in [0, 2^64) per image,
+    validated here before the launch (options.image_seeds) -- image b of the n / B rows each gets the schedule of the
+    call on its rows alone with seed seeds[b] at offset 0 (t2h_unmask_schedule_batch); head_mask is [B, steps + 1] and
+    the increments are those of ONE image's draws."""
     _chk_i64(tex)
     n = tex.numel()
     dev = tex.device
+    if seeds is not None:
+        if not options.is_per_image(seeds) or len(seeds) < 1 or n % len(seeds) != 0:
+            raise ValueError(f'seeds: one integer per image expected, dividing the {n} token rows, got {seeds!r}')
+        B = len(seeds)
+        seeds = options.image_seeds(B, seeds)
+        T = n // B
+        rand_gt, rand_inc = torch_draw_geometry(T, dev)
+        _, expo_inc = torch_draw_geometry(T * n_class, dev)
+        if keep is not None:
+            _chk_u8(keep, n)
+        seeds_dev = seeds_tensor(seeds, dev)
+        step_of_row = torch.empty(n, dtype=torch.int32, device=dev)
+        head_mask = torch.empty((B, steps + 1), dtype=torch.int32, device=dev)
+        check(_lib.load().t2h_unmask_schedule_batch(_p(seeds_dev), rand_gt, rand_inc, expo_inc, _p(tex), _p(keep), B, T,
+                                                    int(steps), int(n_heads), _p(step_of_row), _p(head_mask), _stream()),
+              't2h_unmask_schedule_batch')
+        return step_of_row, head_mask, rand_inc, expo_inc
     rand_gt, rand_inc = torch_draw_geometry(n, dev)
     _, expo_inc = torch_draw_geometry(n * n_class, dev)
     step_of_row = torch.empty(n, dtype=torch.int32, device=dev)
@@ -976,7 +1030,7 @@ def _philox_fields(a, numel, device, **fields):
 
 def sample_heads(hidden, lnf_g, lnf_b, w_heads, expo_by_head, rows, n_rows, tex, temp, x_t, out_idx, split=True,
                  philox=None, hidden_compact=False, row_noise=None, logits_ws=None, top_k=0, top_p=1.0, params=None,
-                 rows_per_sample=None, logp=None, targets=None, rank=None):
+                 rows_per_sample=None, logp=None, targets=None, rank=None, seed_img=None, img_rows=None):
     """All heads in one launch: `rows` (int32, first n_rows valid) are the changed token
     rows, expo_by_head {head: [n, n_class] Exp(1) draw}, w_heads [n_heads, n_class, C],
     out_idx [n_heads, n].  philox = (seed, {head: generator offset}): the noise of the listed heads is
@@ -992,7 +1046,10 @@ def sample_heads(hidden, lnf_g, lnf_b, w_heads, expo_by_head, rows, n_rows, tex,
     also gets the log-probability of its token under the full softmax of logits / temp.
     targets (int64 [n_heads, n], the layout of out_idx; None = off): scoring (t2h_score_heads[_per_sample], DESIGN.md
     4.6g) -- the token of a listed row is read from targets[tex[row]][row] instead of drawn, no noise is read, logp is
-    required; rank (int32, >= n elements, optional): the number of classes with a strictly greater logit."""
+    required; rank (int32, >= n elements, optional): the number of classes with a strictly greater logit.
+    seed_img (int64 [n / img_rows] on the device, seeds_tensor) + img_rows: per-image seeds -- with a
+    'philox' row_noise, listed row r is drawn with seed seed_img[r // img_rows] on row r % img_rows of its own image's
+    [img_rows, n_class] draw (row_noise's seed is not read; its rng_rows, if any, still name the noise row)."""
     _chk_f32(hidden, lnf_g, lnf_b, w_heads, *expo_by_head.values())
     score = None
     if targets is not None:
@@ -1043,14 +1100,23 @@ def sample_heads(hidden, lnf_g, lnf_b, w_heads, expo_by_head, rows, n_rows, tex,
                 rr = row_noise[3]
                 assert rr.dtype == torch.int32 and rr.is_cuda and rr.numel() >= int(n_rows)
                 a.rng_rows = rr.data_ptr()
-            _philox_fields(a, n * n_class, hidden.device, philox_seed=seed)  # (a tensor: the seed of a replayed round)
+            if seed_img is not None:
+                T_img = int(img_rows)
+                assert seed_img.dtype == torch.int64 and seed_img.is_cuda and seed_img.is_contiguous()
+                assert T_img > 0 and seed_img.numel() * T_img == n, (seed_img.numel(), T_img, n)
+                a.philox_seed_img, a.img_rows = seed_img.data_ptr(), T_img
+                a.philox_grid_threads = torch_draw_geometry(T_img * n_class, hidden.device)[0]  # ONE image's draw
+            else:
+                _philox_fields(a, n * n_class, hidden.device, philox_seed=seed)  # (a tensor: the seed of a replayed round)
         else:
+            assert seed_img is None, 'per-image seeds draw in the kernel: no explicit noise'
             _, erows, slots = row_noise
             _chk_f32(erows)
             assert erows.is_contiguous() and erows.shape[-1] == n_class
             assert slots.dtype == torch.int32 and slots.is_cuda and slots.numel() >= int(n_rows)
             a.expo_rows, a.expo_slot = erows.data_ptr(), slots.data_ptr()
     elif philox is not None:
+        assert seed_img is None
         _philox_fields(a, n * n_class, hidden.device, philox_seed=philox[0])
         for h, off in philox[1].items():
             a.philox_offset[h] = int(off)

@@ -215,6 +215,52 @@ def refine_sampling(opt):
     return refine_values(*vals)
 
 
+# Per-image seeds.  Absent key = off = the shared generator stream of the reference.
+def image_seeds(batch, seeds):
+    """The validated `seeds` of a seeded sampling call: one integer in [0, 2^64) per image, in the caller's sample order
+    (a list, a tuple, a 1-D numpy array or a 1-D CPU tensor of integers) -> list of `batch` Python ints.  ValueError
+    naming the image otherwise -- callers check before anything is drawn or launched."""
+    import numbers
+    vals = per_image_values(batch, seeds, 'seeds')
+    if vals is None:
+        raise ValueError(f'seeds: one integer per image expected (a sequence of {int(batch)}), got {seeds!r}')
+    for b, s in enumerate(vals):
+        if isinstance(s, bool) or not isinstance(s, numbers.Integral):
+            raise ValueError(f'seeds, image {b}: an integer expected, got {s!r}')
+        if not 0 <= int(s) < (1 << 64):
+            raise ValueError(f'seeds, image {b}: must lie in [0, 2^64), got {s!r}')
+    return [int(s) for s in vals]
+
+
+def image_seed(manual_seed, img_name):
+    """The seed of one image of a `per_image_seeds` run: the first 8 bytes, big-endian, of
+    SHA-256(f"{manual_seed}:{img_name}") -- a function of the run's seed and the image's name only, not of the dataset
+    order, the batch size, the shard or the rank."""
+    import hashlib
+    return int.from_bytes(hashlib.sha256(f'{manual_seed}:{img_name}'.encode()).digest()[:8], 'big')
+
+
+def per_image_seeding(opt):
+    """-> True iff the option `per_image_seeds` is set (validated: a bool, or absent).  The flag promises that an image
+    does not depend on its batch; the paths that cannot keep that promise yet -- `sample_order: confidence`,
+    `sample_best_of` > 1, any `refine_*` key (those draws come from the shared generator) -- raise ValueError with it."""
+    flag = opt.get('per_image_seeds')
+    if flag is None or flag is False:
+        return False
+    if flag is not True:
+        raise ValueError(f'per_image_seeds must be true or false, got {flag!r}')
+    clash = []
+    if sampling_order(opt) is not None:
+        clash.append('sample_order: confidence')
+    if sampling_best_of(opt) > 1:
+        clash.append('sample_best_of > 1')
+    clash += [k for k in REFINE_KEYS if opt.get(k) is not None]
+    if clash:
+        raise ValueError('per_image_seeds promises images that do not depend on their batch; it cannot be combined with '
+                         + ', '.join(clash) + ' (those draws use the shared generator stream)')
+    return True
+
+
 def dict2str(opt, indent_level=1):
     msg = ''
     pad = ' ' * (indent_level * 2)

@@ -2,9 +2,12 @@
 
 The reference's sample_from_parsing.py entry point on this package: same YAML, same
 dataset tree, same output files ({results_root}/{img_name}).  `--batch-size` overrides the
-reference's hard-coded 4 (larger batches are what the MI355X path is built for; note that
-the images drawn for a batch depend on the batch composition through the shared RNG
-stream, exactly as in the reference).
+reference's hard-coded 4 (larger batches are what the MI355X path is built for).  By default the
+images drawn for a batch depend on the batch composition through the shared RNG stream, exactly
+as in the reference; with `--per-image-seeds` (YAML: `per_image_seeds: true`) every image is
+drawn from a stream of its own, seeded from (`manual_seed`, its `img_name`), and its sampled
+tokens no longer depend on the batch size, the batch it rides in, the shard or the rank
+(DESIGN.md 4.6h).
 
 Several GPUs of one node: launch one process per GPU,
 
@@ -88,6 +91,7 @@ def _setup(opt_path, log_name, rank=0, world=1, dist=None):
             dist.broadcast_object_list(seed, src=0)
         seed = seed[0]
     logger.info(f'Random seed: {seed}')
+    opt['manual_seed'] = seed  # (the run's seed, drawn or given: per_image_seeds derives every image's seed from it)
     options.set_random_seed(seed)  # every rank seeds ITS shard with the run's seed
     return opt, logger
 
@@ -116,6 +120,9 @@ def cli_parser():
     ap.add_argument('--refine-top-p', type=float, default=None,
                     help='refinement: draw every detail code from the most likely classes that hold this share of the '
                          'probability (overrides refine_top_p)')
+    ap.add_argument('--per-image-seeds', action='store_true', default=None,
+                    help='index sampler: draw every image from a stream of its own, seeded from manual_seed and the '
+                         'image\'s name -- an image no longer depends on its batch (sets per_image_seeds)')
     return ap
 
 
@@ -124,13 +131,15 @@ def apply_cli(opt, args):
     checkpoints are read).  Returns opt."""
     for key, v in (('sample_order', args.order), ('confidence_rounds', args.rounds), ('sample_top_k', args.top_k),
                    ('sample_top_p', args.top_p), ('sample_best_of', args.best_of), ('refine_temp', args.refine_temp),
-                   ('refine_top_k', args.refine_top_k), ('refine_top_p', args.refine_top_p)):
+                   ('refine_top_k', args.refine_top_k), ('refine_top_p', args.refine_top_p),
+                   ('per_image_seeds', getattr(args, 'per_image_seeds', None))):
         if v is not None:
             opt[key] = v
     options.sampling_order(opt)
     options.sampling_truncation(opt)
     options.sampling_best_of(opt)
     options.refine_sampling(opt)
+    options.per_image_seeding(opt)
     return opt
 
 

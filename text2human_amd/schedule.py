@@ -53,6 +53,16 @@ def draw_offsets(head_mask, steps, offset0, rand_inc, expo_inc, n_heads):
     return rand_off, expo_off, cur
 
 
+def draw_offsets_per_image(head_mask, steps, rand_inc, expo_inc, n_heads):
+    """draw_offsets for per-image seeds: every image walks its OWN private stream from offset 0 with
+    its own head mask -- head_mask [B, steps + 1], the increments those of one image's draws.  Returns (expo_off int64
+    [B, steps + 1, n_heads], final int64 [B]: where image b's stream ends, the generator offset of the call on image b
+    alone)."""
+    head_mask = np.asarray(head_mask, dtype=np.int64)
+    per = [draw_offsets(m, steps, 0, rand_inc, expo_inc, n_heads) for m in head_mask]
+    return np.stack([p[1] for p in per]), np.array([p[2] for p in per], dtype=np.int64)
+
+
 def _kept_mask(step_of_row, kept):
     """(steps int64 [B*T], kept bool [B*T]).  Without `kept` every row needs a step >= 1; with it (region editing: the
     rows that keep their source token) exactly the kept rows have step 0."""
@@ -127,10 +137,17 @@ def leave_order(step_of_row, B, T, kept=None):
 RoundPlan = namedtuple('RoundPlan', 'perm order start round_steps kept active rng_rows offs')
 
 
-def plan_rounds(step_of_row, tex_host, B, T, compact, shrink, kept=None, expo_off=None):
+def plan_rounds(step_of_row, tex_host, B, T, compact, shrink, kept=None, expo_off=None, per_image=False):
     """What engine.build_schedule decides on the host from what the device hands back (step_of_row, tex_host, kept:
-    [B*T], the caller's order) and draw_offsets' expo_off.  shrink (compact only): finished samples leave the batch."""
+    [B*T], the caller's order) and draw_offsets' expo_off.  shrink (compact only): finished samples leave the batch.
+    per_image (per-image seeds): expo_off is [B, steps + 1, n_heads] (draw_offsets_per_image, the caller's sample
+    order) -- a row's offset is taken from its own image's table and its noise row is local (row % T), reordered batch
+    or not."""
     perm = rng_rows = active = offs = None
+    if per_image and (expo_off is None or np.ndim(expo_off) != 3 or len(expo_off) != B):
+        raise ValueError(f'plan_rounds(per_image=True): expo_off [{B}, steps + 1, n_heads] expected')
+    if not per_image and expo_off is not None and np.ndim(expo_off) != 2:
+        raise ValueError('plan_rounds: expo_off [steps + 1, n_heads] expected (per_image=True takes one table per image)')
     if shrink and compact and B > 1:
         perm, _ = leave_order(step_of_row, B, T, kept)
         if (perm == np.arange(B)).all():
@@ -140,13 +157,19 @@ def plan_rounds(step_of_row, tex_host, B, T, compact, shrink, kept=None, expo_of
         step_of_row, tex_host = step_of_row[orig_row], tex_host[orig_row]
         kept = kept[orig_row] if kept is not None else None
     order, start, round_steps = group_rounds(step_of_row, B, T, compact, kept)
-    if expo_off is not None:
+    if per_image:
+        image = order // T if perm is None else perm[order // T]  # the caller's image of every listed row
+        offs = expo_off[image, step_of_row[order], tex_host[order]]
+        assert (offs >= 0).all()
+    elif expo_off is not None:
         offs = expo_off[step_of_row[order], tex_host[order]]
         assert (offs >= 0).all()
     if shrink and compact:
         active = (round_steps > 0).sum(1).astype(np.int64)
         assert all((round_steps[r, :active[r]] > 0).all() for r in range(len(active)))  # a prefix of the batch
-    if perm is not None:
+    if per_image:
+        rng_rows = (order % T).astype(np.int32)
+    elif perm is not None:
         rng_rows = orig_row[order].astype(np.int32)
     return RoundPlan(perm, order, start, round_steps, kept, active, rng_rows, offs)
 
