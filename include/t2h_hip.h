@@ -446,6 +446,27 @@ int t2h_region_keep(const uint8_t* mask_u8, const float* map_f32, uint64_t label
                     int32_t H, int32_t W, int32_t th, int32_t tw, uint8_t* keep, void* stream);
 int t2h_merge_kept_indices(const int64_t* src_lists, const uint8_t* keep, int64_t* dst_lists, int32_t n,
                            int32_t n_heads, void* stream);
+/* Self-correction.  Token row i of a th x tw map sits at r = i / tw, c = i % tw; its fold for K folds
+ * is (r + c) % 2 (K = 2), (r % 2) * 2 + c % 2 (K = 4), (r % 4) * 2 + c % 2 (K = 8), (r % 4) * 4 + c % 4 (K = 16); any
+ * other K is an error.
+ * t2h_fold_keep: keep_k [K][B][th * tw] (uint8) = 1 iff the row is not in fold k, or keep[b][i] != 0 (keep may be
+ *   NULL) -- the K keep masks of the pseudo-likelihood critic, one launch.
+ * t2h_fold_gather: logp[b][i] = logp_k[fold(i)][b][i] (and rank from rank_k likewise; rank / rank_k may be NULL).
+ * t2h_select_lowest: score f32 [B][T], count int32 [B] -> keep_out uint8 [B][T], n_sel int32 [B].  A row is eligible
+ *   iff its score is not NaN; the order is ascending by value (<, ==; -inf is eligible and the smallest), ties by the
+ *   lower row index; the first m_b = min(max(count[b], 0), eligible_b) rows get keep_out = 0, every other row (every NaN
+ *   row included) 1; n_sel[b] = m_b.  One workgroup per image, T <= 1024 (T2H_ERR_UNSUPPORTED beyond).
+ * t2h_accept_merge: image b takes the candidate -- cur_lists[h][b T + i] = cand_lists[h][b T + i] for all h, i and
+ *   cur_score[b T + i] = cand_score[b T + i] -- iff always != 0 or sum_cand[b] > sum_cur[b]; sum_out[b] = the sum the
+ *   image now has, accepted[b] = 1 / 0.  sum_cur is only read (sum_out must not alias it). */
+int t2h_fold_keep(const uint8_t* keep, int32_t K, int32_t B, int32_t th, int32_t tw, uint8_t* keep_k, void* stream);
+int t2h_fold_gather(const float* logp_k, const int32_t* rank_k, int32_t K, int32_t B, int32_t th, int32_t tw,
+                    float* logp, int32_t* rank, void* stream);
+int t2h_select_lowest(const float* score, const int32_t* count, int32_t B, int32_t T, uint8_t* keep_out,
+                      int32_t* n_sel, void* stream);
+int t2h_accept_merge(const int64_t* cand_lists, const float* cand_score, const float* sum_cand, const float* sum_cur,
+                     int32_t always, int64_t* cur_lists, float* cur_score, float* sum_out, uint8_t* accepted, int32_t B,
+                     int32_t T, int32_t n_heads, void* stream);
 /* Round cursor of a schedule laid out as padded tables [rounds][maxr] (a round's list padded with
  * copies of one of its own rows: sampling a row twice writes the same token twice): copies round
  * r = *round_ctr of rows_tbl (and of aux64_tbl = per-row generator offsets / aux32_tbl = per-row explicit

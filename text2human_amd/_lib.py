@@ -181,6 +181,10 @@ SIGNATURES = {
     't2h_region_keep': (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp,
                                        c_vp]),
     't2h_merge_kept_indices': (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]),
+    't2h_fold_keep': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    't2h_fold_gather': (ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    't2h_select_lowest': (ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    't2h_accept_merge': (ctypes.c_int, [c_vp] * 4 + [c_i32] + [c_vp] * 4 + [c_i32, c_i32, c_i32, c_vp]),
     't2h_schedule_advance': (ctypes.c_int, [c_vp] * 7 + [c_i32, c_vp]),
     't2h_q_sample': (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_vp, c_vp, c_i32, c_i32, c_vp]),
     't2h_masked_ce_heads': (ctypes.c_int, [c_vp] * 9 + [c_i32] * 5 + [c_vp]),

@@ -697,6 +697,94 @@ __global__ void merge_kept_kernel(const int64_t* __restrict__ src, const uint8_t
   if (keep[i % n]) dst[i] = src[i];
 }
 
+// ---- self-correction: the fold lattice of the pseudo-likelihood critic, the choice of the rows to
+// redo and the per-image accept.
+// The fold of token row i of a th x tw map (r = i / tw, c = i % tw): K = 2 a checkerboard, K = 4 / 8 / 16 lattices on
+// which no two 8-neighbours share a fold.
+__device__ __forceinline__ int fold_of_row(int i, int tw, int K) {
+  const int r = i / tw, c = i - r * tw;
+  return K == 2 ? (r + c) & 1 : K == 4 ? (r & 1) * 2 + (c & 1) : K == 8 ? (r & 3) * 2 + (c & 1) : (r & 3) * 4 + (c & 3);
+}
+
+// keep_k[k][b][i] = 1 iff row i is not in fold k, or the caller keeps it (keep may be NULL)
+__global__ void fold_keep_kernel(const uint8_t* __restrict__ keep, int K, int n, int T, int tw,
+                                 uint8_t* __restrict__ keep_k, int64_t total) {
+  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= total) return;
+  const int k = (int)(q / n), j = (int)(q - (int64_t)k * n);
+  keep_k[q] = (fold_of_row(j % T, tw, K) != k || (keep && keep[j] != 0)) ? 1 : 0;
+}
+
+// out[j] = src_k[fold(j)][j]: every row from the evaluation that hid it (logp, and rank where given)
+__global__ void fold_gather_kernel(const float* __restrict__ logp_k, const int32_t* __restrict__ rank_k, int K, int n,
+                                   int T, int tw, float* __restrict__ logp, int32_t* __restrict__ rank) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const int64_t q = (int64_t)fold_of_row(j % T, tw, K) * n + j;
+  logp[j] = logp_k[q];
+  if (rank) rank[j] = rank_k[q];
+}
+
+// The count[b] rows of image b with the lowest score get keep_out = 0 (redo), every other row 1.  A row is eligible iff
+// its score is not NaN; the order is ascending by value (<, ==: -inf is the smallest, +0 and -0 tie), ties by the lower
+// row index.  One workgroup per image, the scores in LDS; a row's place in the order is counted, not sorted, so the
+// result does not depend on the thread count.
+constexpr int SEL_THREADS = 256, SEL_MAX_T = 1024;
+__global__ __launch_bounds__(SEL_THREADS) void select_lowest_kernel(const float* __restrict__ score,
+                                                                   const int32_t* __restrict__ count, int T,
+                                                                   uint8_t* __restrict__ keep_out,
+                                                                   int32_t* __restrict__ n_sel) {
+  __shared__ float s_s[SEL_MAX_T];
+  __shared__ int red[SEL_THREADS / 64];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float* sc = score + (int64_t)b * T;
+  int elig = 0;
+  for (int i = tid; i < T; i += SEL_THREADS) {
+    const float v = sc[i];
+    s_s[i] = v;
+    elig += v == v ? 1 : 0;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) elig += __shfl_xor(elig, o, 64);
+  if (lane == 0) red[wave] = elig;
+  __syncthreads();
+  elig = 0;
+  for (int k = 0; k < SEL_THREADS / 64; ++k) elig += red[k];
+  const int want = count[b] > 0 ? count[b] : 0;
+  const int m = want < elig ? want : elig;
+  for (int i = tid; i < T; i += SEL_THREADS) {
+    const float si = s_s[i];
+    int before = 0;
+    for (int j = 0; j < T; ++j) {
+      const float sj = s_s[j];
+      before += (sj < si || (sj == si && j < i)) ? 1 : 0;  // (a NaN compares false both ways: never before anything)
+    }
+    keep_out[(int64_t)b * T + i] = (si == si && before < m) ? 0 : 1;
+  }
+  if (tid == 0) n_sel[b] = m;
+}
+
+// Image b takes the candidate -- its n_heads index lists and its scores -- iff always, or sum_cand[b] > sum_cur[b]
+// (strictly: an equal sum, a -inf candidate and a NaN keep the current map).  sum_out[b] / accepted[b]: the sum the image
+// now has, and whether it took the candidate; sum_cur is only read.
+__global__ void accept_merge_kernel(const int64_t* __restrict__ cand, const float* __restrict__ cand_score,
+                                    const float* __restrict__ sum_cand, const float* __restrict__ sum_cur, int always,
+                                    int64_t* __restrict__ cur, float* __restrict__ cur_score,
+                                    float* __restrict__ sum_out, uint8_t* __restrict__ accepted, int B, int T,
+                                    int64_t total) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int n = B * T, j = (int)(i % n), b = j / T;
+  const bool take = always || sum_cand[b] > sum_cur[b];
+  if (take) cur[i] = cand[i];
+  if (i < n && take) cur_score[i] = cand_score[i];
+  if (i < B) {
+    const bool tb = always || sum_cand[i] > sum_cur[i];
+    sum_out[i] = tb ? sum_cand[i] : sum_cur[i];
+    accepted[i] = tb ? 1 : 0;
+  }
+}
+
 // ---- round cursor of a pre-computed schedule (engine.sample_tokens, graph replay): copies round
 // r = *round_ctr of the padded [rounds][maxr] tables into fixed staging buffers and advances the
 // counter, so that every round of a sampling run is the SAME launch sequence with the same arguments
@@ -1624,6 +1712,61 @@ extern "C" int t2h_merge_kept_indices(const int64_t* src_lists, const uint8_t* k
   hipLaunchKernelGGL(merge_kept_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), src_lists, keep, dst_lists, n, total);
   T2H_CHECK_LAUNCH("t2h_merge_kept_indices");
+  return T2H_OK;
+}
+
+static bool fold_count_ok(int K) { return K == 2 || K == 4 || K == 8 || K == 16; }
+
+extern "C" int t2h_fold_keep(const uint8_t* keep, int32_t K, int32_t B, int32_t th, int32_t tw, uint8_t* keep_k,
+                             void* stream) {
+  T2H_REQUIRE(keep_k, "t2h_fold_keep: NULL pointer");
+  T2H_REQUIRE(fold_count_ok(K) && B > 0 && th > 0 && tw > 0 && (int64_t)B * th * tw <= 0x7fffffff / 16,
+              "t2h_fold_keep: bad arguments (K=%d B=%d cells %dx%d)", K, B, th, tw);
+  const int T = th * tw, n = B * T;
+  const int64_t total = (int64_t)K * n;
+  hipLaunchKernelGGL(fold_keep_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), keep, K, n, T, tw, keep_k, total);
+  T2H_CHECK_LAUNCH("t2h_fold_keep");
+  return T2H_OK;
+}
+
+extern "C" int t2h_fold_gather(const float* logp_k, const int32_t* rank_k, int32_t K, int32_t B, int32_t th, int32_t tw,
+                               float* logp, int32_t* rank, void* stream) {
+  T2H_REQUIRE(logp_k && logp && (rank == nullptr || rank_k != nullptr), "t2h_fold_gather: NULL pointer");
+  T2H_REQUIRE(fold_count_ok(K) && B > 0 && th > 0 && tw > 0 && (int64_t)B * th * tw <= 0x7fffffff / 16,
+              "t2h_fold_gather: bad arguments (K=%d B=%d cells %dx%d)", K, B, th, tw);
+  const int T = th * tw, n = B * T;
+  hipLaunchKernelGGL(fold_gather_kernel, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), logp_k,
+                     rank_k, K, n, T, tw, logp, rank);
+  T2H_CHECK_LAUNCH("t2h_fold_gather");
+  return T2H_OK;
+}
+
+extern "C" int t2h_select_lowest(const float* score, const int32_t* count, int32_t B, int32_t T, uint8_t* keep_out,
+                                 int32_t* n_sel, void* stream) {
+  T2H_REQUIRE(score && count && keep_out && n_sel, "t2h_select_lowest: NULL pointer");
+  T2H_REQUIRE(B > 0 && T > 0, "t2h_select_lowest: bad arguments (B=%d T=%d)", B, T);
+  if (T > SEL_MAX_T) {
+    t2h_set_error("t2h_select_lowest: T=%d rows per image do not fit the kernel's LDS (at most %d)", T, SEL_MAX_T);
+    return T2H_ERR_UNSUPPORTED;
+  }
+  hipLaunchKernelGGL(select_lowest_kernel, dim3(B), dim3(SEL_THREADS), 0, static_cast<hipStream_t>(stream), score, count,
+                     T, keep_out, n_sel);
+  T2H_CHECK_LAUNCH("t2h_select_lowest");
+  return T2H_OK;
+}
+
+extern "C" int t2h_accept_merge(const int64_t* cand_lists, const float* cand_score, const float* sum_cand,
+                                const float* sum_cur, int32_t always, int64_t* cur_lists, float* cur_score,
+                                float* sum_out, uint8_t* accepted, int32_t B, int32_t T, int32_t n_heads, void* stream) {
+  T2H_REQUIRE(cand_lists && cand_score && sum_cand && sum_cur && cur_lists && cur_score && sum_out && accepted,
+              "t2h_accept_merge: NULL pointer");
+  T2H_REQUIRE(B > 0 && T > 0 && n_heads > 0 && (int64_t)B * T <= 0x7fffffff, "t2h_accept_merge: bad arguments");
+  const int64_t total = (int64_t)B * T * n_heads;
+  hipLaunchKernelGGL(accept_merge_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), cand_lists, cand_score, sum_cand, sum_cur, always ? 1 : 0, cur_lists,
+                     cur_score, sum_out, accepted, B, T, total);
+  T2H_CHECK_LAUNCH("t2h_accept_merge");
   return T2H_OK;
 }
 

@@ -182,6 +182,22 @@ def with_per_image_seeds(opt, on=True):
     return opt
 
 
+def with_revision(opt, passes=0, fraction=None, folds=None):
+    """`opt` with the keys that make sample_and_refine / inference run revise_fn on the sampled token map
+    (options.revise_settings; passes 0 or None: off, the keys are removed; fraction / folds None: their defaults).
+    Returns opt."""
+    from . import options
+    for key in ('revise_passes', 'revise_fraction', 'revise_folds'):
+        opt.pop(key, None)
+    if passes:
+        opt['revise_passes'] = options.revise_passes_value(passes)
+        if fraction is not None:
+            opt['revise_fraction'] = options.revise_fractions(1, fraction)[0]
+        if folds is not None:
+            opt['revise_folds'] = options.revise_folds_value(folds)
+    return opt
+
+
 def write_yaml(opt, path):
     with open(path, 'w') as f:
         yaml.safe_dump(dict(opt), f, sort_keys=False)

@@ -364,10 +364,7 @@ class BaseSampleModel():
     def _score(self, top_indices_list, keep, temp, sample_steps, return_rank, summary, seeds):
         """score_fn / score_fn_seeded"""
         # (everything below raises before anything is evaluated or drawn)
-        if not options.is_per_image(temp) and (isinstance(temp, bool) or not isinstance(temp, numbers.Real) or
-                                               not 0.0 < float(temp) < float('inf')):
-            raise ValueError(f'score_fn: temp must be a finite number > 0, got {temp!r}')
-        ops.sampling_params(self.batch_size, temp)  # (a per-image sequence: its length and every entry)
+        self._score_temp(temp, 'score_fn')
         targets = self._token_lists(top_indices_list, 'score_fn')
         keep = None if keep is None else self._keep_rows(keep)
         out = self._sample(temp, sample_steps or self.sample_steps, score=(targets, keep, bool(return_rank)), seeds=seeds)
@@ -375,6 +372,164 @@ class BaseSampleModel():
         if summary:
             res.append(ops.logp_summary(res[0].contiguous()))
         return res[0] if len(res) == 1 else tuple(res)
+
+    # ------------------------------------------------------------ self-correction
+    # the sampler's own transformer as an order-free critic (pll_fn: K evaluations on a fold lattice),
+    # and the loop that re-masks the rows it likes least, redraws them and keeps what it prefers (revise_fn).
+    @torch.no_grad()
+    def pll_fn(self, top_indices_list, keep=None, folds=4, temp=1.0, return_rank=False, summary=False):
+        """Pseudo-log-likelihood of a GIVEN token map (opt-in): -> pll float32 [B, 512], for every row
+        the log-probability of its token under the full softmax of logits / temp when the transformer sees the map with
+        the non-kept rows of the row's FOLD replaced by the mask token and every other row as given -- on the rows of
+        fold k what score_fn(map, keep=keep_k[k], temp=temp, sample_steps=1) computes.  folds (2, 4, 8 or 16) = the
+        number of transformer evaluations; the lattice is t2h_fold_keep's (for folds >= 4 a hidden row sees all eight
+        neighbours).  Input formats, keep, temp (a scalar or one value per image), return_rank and summary as in
+        score_fn; the rows in keep are NaN / rank -1; a token without an index under the current texture map raises
+        T2HError and nothing is evaluated.  Nothing is drawn: the generator is neither read nor advanced, two calls
+        return the same bits, and an image's numbers do not depend on the batch it is scored in (the arithmetic of
+        per-image seeds)."""
+        folds = options.revise_folds_value(folds)
+        self._score_temp(temp, 'pll_fn')
+        targets = self._token_lists(top_indices_list, 'pll_fn')
+        keep = None if keep is None else self._keep_rows(keep)
+        pll, rank = self._pll(targets, keep, folds, temp, bool(return_rank))
+        b = self.batch_size
+        res = [pll.view(b, -1)] + ([rank.view(b, -1)] if return_rank else [])
+        if summary:
+            res.append(ops.logp_summary(res[0]))
+        return res[0] if len(res) == 1 else tuple(res)
+
+    def _score_temp(self, temp, what):
+        """the temperature of a scoring call, validated: a finite number > 0, or one per image"""
+        if not options.is_per_image(temp) and (isinstance(temp, bool) or not isinstance(temp, numbers.Real) or
+                                               not 0.0 < float(temp) < float('inf')):
+            raise ValueError(f'{what}: temp must be a finite number > 0, got {temp!r}')
+        ops.sampling_params(self.batch_size, temp)  # (a per-image sequence: its length and every entry)
+
+    def _critic_net(self):
+        """The sampler's transformer with buffers and captured rounds of its own (built on first use; shares weights and
+        x8 scales): the critic's batch of K * B images does not replace the buffers sample_fn's captured rounds point to."""
+        s = self.sampler_fn
+        if getattr(self, '_critic', None) is None or self._critic_of is not s:
+            c = engine.SamplerNet(self.P, self._tf_desc, self.opt['bert_n_head'], 'tf', split=s.split,
+                                  split_mha=s.split_mha, x8=s.x8)
+            c._x8 = s.ensure_x8()._x8
+            c.x8 = s.x8  # (a calibration that left fp16's range switched it off)
+            self._critic, self._critic_of = c, s
+        return self._critic
+
+    def _pll(self, targets, keep, folds, temp, want_rank=False):
+        """pll_fn on targets int64 [18, B*512] / keep uint8 [B*512] or None -> (pll f32 [B*512], rank int32 or None).
+        The K evaluations are score_tokens_seeded runs of ONE step (every non-kept row is unmasked -- scored -- by the
+        single round, whatever the seed): through _sample, so its fall-back chain applies; the seeded form neither reads
+        nor advances the generator and computes every image as the call on it alone would."""
+        b, t_len, cells = self.batch_size, self.shape[0] * self.shape[1], tuple(self.shape)
+        n = b * t_len
+        tex_flat = self._texture_tokens(self.texture_mask).reshape(-1)
+        n_class = self.P['tf.heads'].shape[1]
+        engine._target_check(targets, tex_flat, n_class, t_len)  # (names the caller's (sample, row); nothing evaluated)
+        keep_k = ops.fold_keep(folds, b, cells, keep, device=self.device)
+        logp_k = torch.empty((folds, n), dtype=torch.float32, device=self.device)
+        rank_k = torch.empty((folds, n), dtype=torch.int32, device=self.device) if want_rank else None
+        saved = (self.batch_size, self.segm_tokens, self.texture_mask, self.noise, self.sampler_fn,
+                 getattr(self, 'last_seed_offsets', None))
+        try:
+            self.noise = None  # (nothing is drawn: an explicit noise source has no say here)
+            if options.pll_batched(b, folds):
+                # one batch of K * B images: image k * B + j = image j with fold k hidden
+                self.batch_size = folds * b
+                self.segm_tokens = self.segm_tokens.repeat(folds, 1)
+                self.texture_mask = self.texture_mask.repeat(folds, 1, 1, 1)
+                self.sampler_fn = self._critic_net()
+                t_kb = targets.view(-1, 1, n).expand(-1, folds, n).reshape(targets.shape[0], folds * n).contiguous()
+                temp_kb = list(options.per_image_values(b, temp, 'temp')) * folds if options.is_per_image(temp) else temp
+                out = self._sample(temp_kb, 1, score=(t_kb, keep_k.view(-1), want_rank), seeds=[0] * (folds * b))
+                logp_k = (out[0] if want_rank else out).reshape(folds, n).contiguous()
+                rank_k = out[1].reshape(folds, n).contiguous() if want_rank else None
+            else:
+                for k in range(folds):
+                    out = self._sample(temp, 1, score=(targets, keep_k[k].view(-1), want_rank), seeds=[0] * b)
+                    logp_k[k].copy_((out[0] if want_rank else out).reshape(-1))
+                    if want_rank:
+                        rank_k[k].copy_(out[1].reshape(-1))
+        finally:
+            (self.batch_size, self.segm_tokens, self.texture_mask, self.noise, self.sampler_fn,
+             self.last_seed_offsets) = saved
+        out = ops.fold_gather(logp_k, folds, b, cells, rank_k=rank_k)
+        return out if want_rank else (out, None)
+
+    _FRACTION_DEFAULT = float(options.REVISE_FRACTION)  # (the default OBJECT: tells "not given" from a given 0.25)
+
+    @torch.no_grad()
+    def revise_fn(self, top_indices_list, passes=1, fraction=_FRACTION_DEFAULT, count=None, keep=None, folds=4,
+                  accept='improve', temp=1.0, critic_temp=1.0, sample_steps=None, order='random', rounds=None,
+                  choice_temp=4.5, top_k=None, top_p=None, seeds=None, return_trace=False):
+        """Self-correction of a GIVEN token map (opt-in) -> 18 x int64 [B, 512] in sample_fn's format,
+        with return_trace (lists, trace).  Every pass: the m_b rows of image b with the lowest pll_fn(map, keep, folds,
+        critic_temp) are re-masked (t2h_select_lowest) and redrawn given everything else (resample_fn with temp /
+        sample_steps / order / rounds / choice_temp / top_k / top_p), the candidate is scored by the same critic, and --
+        accept='improve' -- image b takes it iff the t2h_logp_summary sum of its pll is STRICTLY greater (accept='always':
+        every image takes it).  m_b = min(count, eligible_b) with count (an integer or one per image), else
+        max(1, floor(fraction * eligible_b + 0.5)), eligible_b = the rows of image b not in keep (0 rows: nothing is
+        redone; if that holds for every image the pass makes no resample_fn call); fraction in (0, 1], a scalar or one
+        per image; giving both is a ValueError.  keep [B, 512]: rows that are given -- never scored, selected or redrawn.
+        seeds (order='random' only): pass p redraws image b with (seeds[b] + p) mod 2^64, as resample_fn does; the
+        global generator does not move.  Without seeds it moves exactly as the resample_fn calls move it.
+        trace: one dict per pass -- selected uint8 [B, 512] (1 = redrawn), sum_before / sum_after f32 [B], accepted
+        bool [B].  With accept='improve' the summary sum of pll_fn(result, keep, folds, critic_temp) is >= that of
+        pll_fn(input, ...) for every image.  What the critic prefers is the model's own judgement, nothing more: no
+        claim about image quality is made."""
+        # (everything below raises before anything is evaluated or drawn)
+        passes = options.revise_passes_value(passes)
+        folds = options.revise_folds_value(folds)
+        always = options.revise_accept_value(accept) == 'always'
+        if count is not None and fraction is not self._FRACTION_DEFAULT:
+            raise ValueError('revise_fn: give either fraction or count, not both')
+        self._score_temp(critic_temp, 'revise_fn (critic_temp)')
+        if order not in ('random', 'confidence'):
+            raise ValueError(f"order must be 'random' or 'confidence', got {order!r}")
+        if order == 'confidence':
+            self._no_seeds(seeds, "revise_fn(order='confidence')")
+        if seeds is not None:
+            seeds = options.image_seeds(self.batch_size, seeds)
+        ops.sampling_params(self.batch_size, temp, top_k, top_p)
+        b, t_len = self.batch_size, self.shape[0] * self.shape[1]
+        keep_rows = None if keep is None else self._keep_rows(keep)
+        eligible = [t_len] * b if keep_rows is None else [t_len - int(x) for x in
+                                                          (keep_rows.view(b, t_len) != 0).sum(1).tolist()]
+        m = options.revise_row_counts(eligible, None if count is not None else fraction, count)
+        cur = self._token_lists(top_indices_list, 'revise_fn').clone()
+        m_dev = torch.tensor(m, dtype=torch.int32).to(self.device)
+        cur_pll = self._pll(cur, keep_rows, folds, critic_temp)[0]
+        cur_sum = ops.logp_summary(cur_pll, b, t_len)[0]
+        steps = []  # per pass: (sel_keep or None, sum_before, sum_after, accepted uint8 or None)
+        for p in range(passes):
+            if not any(m):
+                steps.append((None, cur_sum, cur_sum, None))
+                continue
+            # (from the candidate's scoring to this selection: kernels of the library only, nothing read back)
+            sel_keep, _ = ops.select_lowest(cur_pll.view(b, t_len), m_dev)
+            seed_kw = {} if seeds is None else dict(seeds=[(s + p) % (1 << 64) for s in seeds])
+            cand = self._token_lists(self.resample_fn(cur, sel_keep, temp=temp, sample_steps=sample_steps, order=order,
+                                                      rounds=rounds, choice_temp=choice_temp, top_k=top_k, top_p=top_p,
+                                                      **seed_kw), 'revise_fn')
+            cand_pll = self._pll(cand, keep_rows, folds, critic_temp)[0]
+            cand_sum = ops.logp_summary(cand_pll, b, t_len)[0]
+            new_sum, accepted = ops.accept_merge(cand, cand_pll, cand_sum, cur, cur_pll, cur_sum, b, always=always)
+            steps.append((sel_keep, cur_sum, cand_sum, accepted))
+            cur_sum = new_sum
+        lists = [cur[i].view(b, -1) for i in range(cur.shape[0])]
+        if not return_trace:
+            return lists
+        trace = []
+        for sel_keep, before, after, accepted in steps:
+            if sel_keep is None:
+                selected = torch.zeros((b, t_len), dtype=torch.uint8, device=self.device)
+                accepted = torch.full((b, ), always, dtype=torch.bool, device=self.device)
+            else:
+                selected, accepted = 1 - sel_keep, accepted != 0
+            trace.append(dict(selected=selected, sum_before=before, sum_after=after, accepted=accepted))
+        return lists, trace
 
     @torch.no_grad()
     def edit_and_refine(self, top_indices_list, region=None, labels=None, bot_indices_list=None, save_dir=None,
@@ -587,7 +742,9 @@ class BaseSampleModel():
         """models/sample_model.py:215-254.  With both arguments None returns the
         first sample as f32 [1,3,512,256] in [0,1] (what ui_demo.py:162 uses);
         otherwise writes {save_dir}/{img_name[i]} PNGs.  seeds (options: per_image_seeds, derived by inference();
-        DESIGN.md 4.6h): the top indices of image b are sample_fn's with seeds[b]."""
+        DESIGN.md 4.6h): the top indices of image b are sample_fn's with seeds[b].  With the option `revise_passes` > 0
+         the sampled map goes through revise_fn -- `revise_fraction`, `revise_folds`, the run's
+        truncation / order settings and `seeds` -- before the bottom indices are predicted."""
         if seeds is not None:
             seeds = options.image_seeds(self.batch_size, seeds)
             options.per_image_seeding(dict(self.opt, per_image_seeds=True))  # (the options that cannot keep the promise)
@@ -596,6 +753,7 @@ class BaseSampleModel():
         trunc = {k: v for k, v in (('top_k', top_k), ('top_p', top_p)) if v is not None}
         refine_kw = self._refine_options()  # (options: refine_temp / refine_top_k / refine_top_p)
         best_of = options.sampling_best_of(self.opt)  # (options: sample_best_of; 1: the calls below, as always)
+        revise = options.revise_settings(self.opt)  # (options: revise_passes / revise_fraction / revise_folds; None: off)
         if best_of > 1:
             kw = dict(trunc, temp=1)
             if confidence is not None:
@@ -614,6 +772,14 @@ class BaseSampleModel():
             sampled_top_indices_list = self.sample_fn(temp=1, sample_steps=self.sample_steps, **trunc, **seed_kw)
         else:
             sampled_top_indices_list = self.sample_fn(temp=1, sample_steps=self.sample_steps)
+        if revise is not None:  # (options: revise_passes > 0)
+            kw = dict(trunc, temp=1, sample_steps=self.sample_steps)
+            if confidence is not None:
+                kw.update(order='confidence', rounds=confidence[0], choice_temp=confidence[1])
+            if seeds is not None:
+                kw.update(seeds=seeds)
+            sampled_top_indices_list = self.revise_fn(sampled_top_indices_list, passes=revise[0], fraction=revise[1],
+                                                      folds=revise[2], **kw)
         want_files = not (save_dir is None and img_name is None)
         if not want_files:
             keep_b, keep_mask = self.batch_size, self.texture_mask

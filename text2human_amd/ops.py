@@ -919,6 +919,69 @@ def merge_kept_indices(src_lists, keep, dst_lists):
     return dst_lists
 
 
+def fold_keep(folds, B, cells, keep=None, device=None):
+    """The K keep masks of the pseudo-likelihood critic (t2h_fold_keep) -> uint8 [K, B, th * tw]: 1 iff
+    the row is not in fold k or the caller keeps it (keep: uint8 [B * th * tw] or None).  folds: options.REVISE_FOLDS."""
+    th, tw = cells
+    folds = options.revise_folds_value(folds)
+    n = int(B) * th * tw
+    if keep is not None:
+        _chk_u8(keep, n)
+        device = keep.device
+    keep_k = torch.empty((int(folds), int(B), th * tw), dtype=torch.uint8, device=device)
+    check(_lib.load().t2h_fold_keep(_p(keep), int(folds), int(B), th, tw, _p(keep_k), _stream()), 't2h_fold_keep')
+    return keep_k
+
+
+def fold_gather(logp_k, folds, B, cells, rank_k=None):
+    """Every row from the evaluation that hid it (t2h_fold_gather): logp_k f32 [K, B * T] (rank_k int32 likewise, or
+    None) -> logp f32 [B * T] (, rank int32 [B * T])."""
+    th, tw = cells
+    n = int(B) * th * tw
+    _chk_f32(logp_k)
+    assert logp_k.is_contiguous() and logp_k.numel() == int(folds) * n
+    logp = torch.empty(n, dtype=torch.float32, device=logp_k.device)
+    rank = None
+    if rank_k is not None:
+        assert rank_k.dtype == torch.int32 and rank_k.is_contiguous() and rank_k.numel() == int(folds) * n
+        rank = torch.empty(n, dtype=torch.int32, device=logp_k.device)
+    check(_lib.load().t2h_fold_gather(_p(logp_k), _p(rank_k), int(folds), int(B), th, tw, _p(logp), _p(rank), _stream()),
+          't2h_fold_gather')
+    return logp if rank is None else (logp, rank)
+
+
+def select_lowest(score, count):
+    """The rows to redo (t2h_select_lowest): score f32 [B, T] (NaN = not eligible), count int32 [B] -> (keep_out uint8
+    [B, T]: 0 for the min(count[b], eligible_b) lowest-scored rows of image b -- ties to the lower row --, 1 elsewhere;
+    n_sel int32 [B]).  Nothing is read back."""
+    _chk_f32(score)
+    B, T = score.shape
+    assert score.is_contiguous() and count.dtype == torch.int32 and count.is_cuda and count.numel() == B
+    keep_out = torch.empty((B, T), dtype=torch.uint8, device=score.device)
+    n_sel = torch.empty(B, dtype=torch.int32, device=score.device)
+    check(_lib.load().t2h_select_lowest(_p(score), _p(count), B, T, _p(keep_out), _p(n_sel), _stream()),
+          't2h_select_lowest')
+    return keep_out, n_sel
+
+
+def accept_merge(cand_lists, cand_score, sum_cand, cur_lists, cur_score, sum_cur, B, always=False):
+    """Per-image accept (t2h_accept_merge, in place on cur_lists int64 [n_heads, B * T] / cur_score f32 [B * T]): image
+    b takes the candidate's lists and scores iff always or sum_cand[b] > sum_cur[b] -> (sum_out f32 [B], accepted uint8
+    [B])."""
+    _chk_i64(cand_lists, cur_lists)
+    _chk_f32(cand_score, cur_score, sum_cand, sum_cur)
+    n_heads, n = cur_lists.shape
+    B = int(B)
+    assert tuple(cand_lists.shape) == (n_heads, n) and n % B == 0 and cand_score.numel() == n == cur_score.numel()
+    assert cand_score.is_contiguous() and cur_score.is_contiguous() and sum_cand.numel() == B == sum_cur.numel()
+    sum_out = torch.empty(B, dtype=torch.float32, device=cur_lists.device)
+    accepted = torch.empty(B, dtype=torch.uint8, device=cur_lists.device)
+    check(_lib.load().t2h_accept_merge(_p(cand_lists), _p(cand_score), _p(sum_cand), _p(sum_cur), int(bool(always)),
+                                       _p(cur_lists), _p(cur_score), _p(sum_out), _p(accepted), B, n // B, n_heads,
+                                       _stream()), 't2h_accept_merge')
+    return sum_out, accepted
+
+
 def schedule_advance(rows_tbl, aux64_tbl, aux32_tbl, round_ctr, cur_rows, cur_aux64, cur_aux32, maxr):
     """Round cursor (t2h_schedule_advance): cur_* <- round *round_ctr of the padded tables; *round_ctr += 1."""
     check(_lib.load().t2h_schedule_advance(_p(rows_tbl), _p(aux64_tbl), _p(aux32_tbl), _p(round_ctr), _p(cur_rows),

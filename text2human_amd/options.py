@@ -261,6 +261,91 @@ def per_image_seeding(opt):
     return True
 
 
+# Self-correction.  `revise_passes` absent or 0 = off = today's run.
+REVISE_FOLDS = (2, 4, 8, 16)
+REVISE_ACCEPT = ('improve', 'always')
+REVISE_FRACTION, REVISE_FOLDS_DEFAULT = 0.25, 4
+PLL_BATCH_MAX = 32  # the critic's K evaluations run as ONE batch of K * B images while K * B <= this
+
+
+def pll_batched(batch, folds):
+    """True: the K evaluations of the pseudo-likelihood critic run as one batch of K * B images; False: as K calls at
+    batch B.  A function of (B, K) alone."""
+    return int(batch) * int(folds) <= PLL_BATCH_MAX
+
+
+def revise_folds_value(folds):
+    """the validated fold count of pll_fn / revise_fn (ValueError otherwise)"""
+    if isinstance(folds, bool) or folds not in REVISE_FOLDS:
+        raise ValueError(f'folds must be one of {REVISE_FOLDS}, got {folds!r}')
+    return int(folds)
+
+
+def revise_passes_value(passes, allow_zero=False):
+    import numbers
+    if isinstance(passes, bool) or not isinstance(passes, numbers.Integral) or int(passes) < (0 if allow_zero else 1):
+        raise ValueError(f'revise passes must be an integer >= {0 if allow_zero else 1}, got {passes!r}')
+    return int(passes)
+
+
+def revise_fractions(batch, fraction):
+    """fraction of revise_fn: a number in (0, 1], or one per image -> list of `batch` floats (ValueError otherwise)"""
+    import numbers
+    vals = per_image_values(batch, fraction, 'fraction')
+    out = []
+    for b, f in enumerate([fraction] * int(batch) if vals is None else vals):
+        if isinstance(f, bool) or not isinstance(f, numbers.Real) or not 0.0 < float(f) <= 1.0:
+            raise ValueError(f'fraction{"" if vals is None else f", image {b}"}: must lie in (0, 1], got {f!r}')
+        out.append(float(f))
+    return out
+
+
+def revise_counts(batch, count):
+    """count of revise_fn: an integer >= 0, or one per image -> list of `batch` ints (ValueError otherwise)"""
+    import numbers
+    vals = per_image_values(batch, count, 'count')
+    out = []
+    for b, c in enumerate([count] * int(batch) if vals is None else vals):
+        if isinstance(c, bool) or not isinstance(c, numbers.Integral) or not 0 <= int(c) <= 0x7fffffff:
+            raise ValueError(f'count{"" if vals is None else f", image {b}"}: must be an integer >= 0, got {c!r}')
+        out.append(int(c))
+    return out
+
+
+def revise_row_counts(eligible, fraction=None, count=None):
+    """Rows revise_fn redoes per image and pass: eligible = the rows of every image the caller does not keep.  With count
+    min(count, eligible_b); otherwise max(1, floor(fraction * eligible_b + 0.5)) in float64, 0 where eligible_b = 0.
+    Exactly one of fraction / count (validated here: ValueError)."""
+    import math
+    if (fraction is None) == (count is None):
+        raise ValueError('revise: give either fraction or count, not both')
+    batch = len(eligible)
+    if count is not None:
+        return [min(c, int(e)) for c, e in zip(revise_counts(batch, count), eligible)]
+    return [0 if int(e) == 0 else max(1, int(math.floor(f * float(int(e)) + 0.5)))
+            for f, e in zip(revise_fractions(batch, fraction), eligible)]
+
+
+def revise_accept_value(accept):
+    if accept not in REVISE_ACCEPT:
+        raise ValueError(f'accept must be one of {REVISE_ACCEPT}, got {accept!r}')
+    return accept
+
+
+def revise_settings(opt):
+    """-> None (no `revise_passes` key, or 0: off) or (passes, fraction, folds) of the options `revise_passes` /
+    `revise_fraction` (default 0.25) / `revise_folds` (default 4), validated.  The options are scalars, one value for
+    the whole run; all three are validated whether the feature is on or not.  `opt` is not changed."""
+    passes = opt.get('revise_passes')
+    passes = 0 if passes is None else revise_passes_value(passes, allow_zero=True)
+    fraction, folds = opt.get('revise_fraction'), opt.get('revise_folds')
+    if is_per_image(fraction):
+        raise ValueError(f'revise_fraction: the option is one value for the whole run, got {fraction!r}')
+    fraction = revise_fractions(1, REVISE_FRACTION if fraction is None else fraction)[0]
+    folds = revise_folds_value(REVISE_FOLDS_DEFAULT if folds is None else folds)
+    return (passes, fraction, folds) if passes > 0 else None
+
+
 def dict2str(opt, indent_level=1):
     msg = ''
     pad = ' ' * (indent_level * 2)

@@ -123,6 +123,16 @@ def cli_parser():
     ap.add_argument('--per-image-seeds', action='store_true', default=None,
                     help='index sampler: draw every image from a stream of its own, seeded from manual_seed and the '
                          'image\'s name -- an image no longer depends on its batch (sets per_image_seeds)')
+    ap.add_argument('--revise-passes', type=int, default=None,
+                    help='index sampler: self-correction passes on the sampled token map -- re-mask the tokens the '
+                         'model\'s own pseudo-likelihood likes least, redraw them, keep the result where that '
+                         'likelihood rose (overrides revise_passes; 0: off)')
+    ap.add_argument('--revise-fraction', type=float, default=None,
+                    help='self-correction: share of an image\'s tokens a pass redraws, in (0, 1] (overrides '
+                         'revise_fraction; default 0.25)')
+    ap.add_argument('--revise-folds', type=int, choices=options.REVISE_FOLDS, default=None,
+                    help='self-correction: folds of the critic\'s lattice = its evaluations per scoring (overrides '
+                         'revise_folds; default 4)')
     return ap
 
 
@@ -132,7 +142,10 @@ def apply_cli(opt, args):
     for key, v in (('sample_order', args.order), ('confidence_rounds', args.rounds), ('sample_top_k', args.top_k),
                    ('sample_top_p', args.top_p), ('sample_best_of', args.best_of), ('refine_temp', args.refine_temp),
                    ('refine_top_k', args.refine_top_k), ('refine_top_p', args.refine_top_p),
-                   ('per_image_seeds', getattr(args, 'per_image_seeds', None))):
+                   ('per_image_seeds', getattr(args, 'per_image_seeds', None)),
+                   ('revise_passes', getattr(args, 'revise_passes', None)),
+                   ('revise_fraction', getattr(args, 'revise_fraction', None)),
+                   ('revise_folds', getattr(args, 'revise_folds', None))):
         if v is not None:
             opt[key] = v
     options.sampling_order(opt)
@@ -140,6 +153,7 @@ def apply_cli(opt, args):
     options.sampling_best_of(opt)
     options.refine_sampling(opt)
     options.per_image_seeding(opt)
+    options.revise_settings(opt)
     return opt
 
 
