@@ -636,6 +636,34 @@ int t2h_vq_argmin_tex_f32(const float* z, const float* books, const int64_t* tex
                           int32_t n, int32_t n_books, int32_t n_e, int32_t d, int32_t fold_h,
                           int32_t fold_w, void* stream);
 
+/* All-codebook fit (opt-in, not in the reference): how well EVERY texture codebook quantises a latent
+ * row.  z: [n][d] latent rows (what t2h_vq_argmin_tex_f32 sees, no fold); books: [n_books][n_e][d]; d == 256 only
+ * (anything else: T2H_ERR_UNSUPPORTED).
+ *   dmin[r][h] = min_j ((sum z_r^2 + sum e_hj^2) - 2 z_r.e_hj)   f32 [n][n_books], the expanded form of
+ *                VectorQuantizer.forward, not clamped;
+ *   jmin[r][h] = the smallest j that attains it                  i32 [n][n_books]; may be NULL.
+ * A (row, book) without a finite comparable distance (NaN / Inf latents): dmin = +inf, jmin = -1.
+ * Products and accumulation are exact fp32 on v_mfma_f32_32x32x2_f32 in ONE fixed k order for every row and code,
+ * independent of n, of the row's position and of the grid: a row's outputs are a function of that row and the books
+ * alone (bit for bit the same alone or in any batch).  The distance matrix is never written; no atomics. */
+int t2h_vq_fit_books_f32(const float* z, const float* books, float* dmin, int32_t* jmin, int32_t n,
+                         int32_t n_books, int32_t n_e, int32_t d, void* stream);
+/* Row tile of t2h_vq_fit_books_f32 for the calling thread: 32, 64 or 128 rows per workgroup, anything else = automatic
+ * (from n and n_books).  Changes speed only, never a bit of the result (tests run every tile).  Returns the old value. */
+int t2h_vq_fit_force_tile(int rows);
+
+/* Region vote over the fit.  dmin: [B*T][n_books] as t2h_vq_fit_books_f32 writes it; segm_tok: [B][T]
+ * parsing labels of the token cells.  Groups as t2h_texture_map: g = 0 upper {1, 4}, 1 lower {3, 5, 21}, 2 outer {2}.
+ *   cost[b][g][h] = sum over the rows of image b whose label is in group g, in ascending row order, of
+ *                   (double)dmin[row][h]                          f64 [B][3][n_books]
+ *   count[b][g]   = the number of such rows                        i32 [B][3]
+ *   attr[b][g]    = first h with the least cost, mapped back by the inverse of the mask rule (h == 0 -> 17 = NA, else
+ *                   h - 1); count == 0 or no cost below +inf -> 17  i64 [B][3]
+ * One workgroup per (image, group), fixed summation order: bit-reproducible and independent of the batch.
+ * n_books <= 64. */
+int t2h_texture_vote(const float* dmin, const int64_t* segm_tok, int32_t B, int32_t T, int32_t n_books,
+                     double* cost, int32_t* count, int64_t* attr, void* stream);
+
 /* VectorQuantizerTexture.get_codebook_entry, vqgan_arch.py:289-309:
  * out[row, :] = books[tex[row]][idx[tex[row]][row]]  (idx_lists: [18, n]) */
 int t2h_codebook_gather_tex_f32(const int64_t* idx_lists, const int64_t* tex,

@@ -44,6 +44,26 @@ def read_fused_annotations(ann_dir):
     return names, attrs
 
 
+def write_fused_annotations(ann_dir, names, upper, lower, outer):
+    """Inverse of read_fused_annotations: writes <ann_dir>/{upper,lower,outer}_fused.txt, one
+    "<image name> <attribute id>" line per image (attribute ids 0..17, 17 = none)."""
+    names = list(names)
+    parts = {}
+    for (part, _), values in zip(GARMENT_CLASSES, (upper, lower, outer)):
+        values = [int(v) for v in (values.tolist() if hasattr(values, 'tolist') else values)]
+        if len(values) != len(names):
+            raise ValueError(f'{part}: {len(values)} attributes for {len(names)} images')
+        if any(v < 0 or v > NO_ATTRIBUTE for v in values):
+            raise ValueError(f'{part}: attribute ids must lie in 0..{NO_ATTRIBUTE}')
+        parts[part] = values
+    if any(len(str(nm).split()) != 1 for nm in names):
+        raise ValueError('image names must be non-empty and free of white space')
+    os.makedirs(ann_dir, exist_ok=True)
+    for part, values in parts.items():
+        with open(os.path.join(ann_dir, f'{part}_fused.txt'), 'w') as f:
+            f.writelines(f'{nm} {v}\n' for nm, v in zip(names, values))
+
+
 def _load(path, factor, resample):
     with open(path, 'rb') as f:
         im = Image.open(f)

@@ -44,18 +44,85 @@ class VQGANTextureAwareSpatialHierarchyInferenceModel():
     def _image_rows(self, x):
         return ops.nchw_to_nhwc(x.to(self.device, torch.float32), cpad=self.cin_pad)
 
-    # ------------------------------------------------------------ reference surface
-    @torch.no_grad()
-    def top_encode(self, x, mask):
-        """-> (quant, quant): f32 [B, 256, 32, 16] after top_post_quant_conv (:170-176)."""
+    def _top_latents(self, x):
+        """image -> (latent rows [B*h*w, 256] after top_quant_conv -- what the codebooks see --, (B, h, w))."""
         P = self.P
         b, _, hh, ww = x.shape
         z, h, w = self.top_encoder.encode(self._image_rows(x), b, hh, ww)
         z = ops.gemm(z, P['top.qc.w'], bias=P['top.qc.b'])
-        tex = self._tex_tokens(mask.to(self.device), h, w)
-        self._top_latent_rows = z  # [B*h*w, 256] what the codebooks see (parity tests account near-ties on it)
-        self.top_indices_list = ops.vq_argmin_tex(z, P['top.books'], tex)
-        quant = self.quant_from_top_indices(self.top_indices_list, mask, (b, h, w))
+        self._top_latent_rows = z  # (parity tests account near-ties on it)
+        return z, (b, h, w)
+
+    def _top_quantize(self, z, bhw, mask):
+        tex = self._tex_tokens(mask.to(self.device), bhw[1], bhw[2])
+        self.top_indices_list = ops.vq_argmin_tex(z, self.P['top.books'], tex)
+        return self.quant_from_top_indices(self.top_indices_list, mask, bhw)
+
+    def _segm_ids(self, segm):
+        """class-id map as the datasets deliver it (f32 or i64 [B, 1, H, W]) -> contiguous i64 on the device"""
+        if segm.dim() != 4 or segm.shape[1] != 1:
+            raise ValueError(f'segm must be [B, 1, H, W], got {tuple(segm.shape)}')
+        return segm.to(self.device).long().contiguous()
+
+    def _vote_attributes(self, z, bhw, segm, return_costs):
+        """the fit of every top codebook to the latent rows, summed per garment region"""
+        b, h, w = bhw
+        if segm.shape[0] != b:
+            raise ValueError(f'segm holds {segm.shape[0]} maps for {b} images')
+        hh, ww = segm.shape[2:]
+        # the cell's source pixel: the one F.interpolate(mask, (h, w), 'nearest') routes the encoder by (_tex_tokens)
+        segm_tok = segm[:, 0, ::hh // h, ::ww // w].reshape(b, -1).contiguous()
+        dmin, _ = ops.vq_fit_books(z, self.P['top.books'], want_index=False)
+        cost, count, attr = ops.texture_vote(dmin, segm_tok, b)
+        out = dict(upper_fused_attr=attr[:, 0].contiguous(), lower_fused_attr=attr[:, 1].contiguous(),
+                   outer_fused_attr=attr[:, 2].contiguous())
+        if return_costs:
+            out.update(cost=cost, count=count)
+        return out
+
+    # ------------------------------------------------------------ un-annotated photos (DESIGN.md 4.6j; opt-in)
+    @torch.no_grad()
+    def infer_texture_attributes(self, image, segm, return_costs=False):
+        """The three texture attributes of a photo that has a parsing map but no annotation: for each garment region
+        (upper {1, 4}, lower {3, 5, 21}, outer {2}) the texture codebook that quantises the region's top latents with
+        the least summed error; 17 (none) for an absent region or when the common codebook fits best.
+        -> dict upper_fused_attr / lower_fused_attr / outer_fused_attr (i64 [B], on the device), texture_mask (f32
+        [B, 1, H, W]); with return_costs also cost f64 [B, 3, 18] (by mask value: 0 = common, attribute + 1) and
+        count i32 [B, 3] (token cells per region).  No host synchronisation."""
+        z, bhw = self._top_latents(image)
+        segm = self._segm_ids(segm)
+        out = self._vote_attributes(z, bhw, segm, return_costs)
+        out['texture_mask'] = ops.texture_map(segm, out['upper_fused_attr'], out['lower_fused_attr'],
+                                              out['outer_fused_attr'])
+        return out
+
+    @torch.no_grad()
+    def encode_photo(self, image, segm, attrs=None):
+        """image + parsing map -> everything region editing, score_fn / pll_fn and revise_fn need: the dict of
+        infer_texture_attributes (attributes taken from `attrs`, a dict of the three, when given) plus
+        top_indices_list ([18, B*512]) and bot_indices_list (18 x i64 [B, 32, 16]) -- exactly what top_encode /
+        bot_encode return for the returned texture_mask.  The top encoder runs once."""
+        z, bhw = self._top_latents(image)
+        segm = self._segm_ids(segm)
+        keys = ('upper_fused_attr', 'lower_fused_attr', 'outer_fused_attr')
+        if attrs is None:
+            out = self._vote_attributes(z, bhw, segm, False)
+        else:
+            out = {k: torch.as_tensor(attrs[k]).to(self.device, torch.long).reshape(-1).contiguous() for k in keys}
+            if any(out[k].numel() != bhw[0] for k in keys):
+                raise ValueError(f'attrs must hold one value per image ({bhw[0]})')
+        mask = out['texture_mask'] = ops.texture_map(segm, *(out[k] for k in keys))
+        self.quant_t = self.feature_t = self._top_quantize(z, bhw, mask)
+        out['top_indices_list'] = self.top_indices_list
+        out['bot_indices_list'] = self.bot_encode(image, mask)
+        return out
+
+    # ------------------------------------------------------------ reference surface
+    @torch.no_grad()
+    def top_encode(self, x, mask):
+        """-> (quant, quant): f32 [B, 256, 32, 16] after top_post_quant_conv (:170-176)."""
+        z, bhw = self._top_latents(x)
+        quant = self._top_quantize(z, bhw, mask)
         return quant, quant
 
     @torch.no_grad()

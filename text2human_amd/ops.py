@@ -1363,6 +1363,44 @@ def vq_argmin_tex(z, books, tex, fold_hw=None):
     return out
 
 
+def vq_fit_books(z, books, want_index=True):
+    """All-codebook fit.  z: latent rows [n, 256]; books [n_books, n_e, 256].  Returns
+    (dmin f32 [n, n_books], jmin i32 [n, n_books] or None): per row and book the least expanded distance and the
+    first code that attains it (+inf / -1 where no code gives a comparable distance)."""
+    _chk_f32(z, books)
+    nb, n_e, d = books.shape
+    assert z.dim() == 2 and z.shape[1] == d, (tuple(z.shape), d)
+    assert z.is_contiguous() and books.is_contiguous()
+    n = z.shape[0]
+    dmin = torch.empty((n, nb), device=z.device, dtype=torch.float32)
+    jmin = torch.empty((n, nb), device=z.device, dtype=torch.int32) if want_index else None
+    check(_lib.load().t2h_vq_fit_books_f32(_p(z), _p(books), _p(dmin), _p(jmin), n, nb, n_e, d, _stream()),
+          't2h_vq_fit_books_f32')
+    return dmin, jmin
+
+
+def vq_fit_force_tile(rows):
+    """Row tile of vq_fit_books for the calling thread (32 / 64 / 128; 0 = automatic).  Returns the old value."""
+    return _lib.load().t2h_vq_fit_force_tile(int(rows))
+
+
+def texture_vote(dmin, segm_tok, B):
+    """Region vote over a fit.  dmin f32 [B*T, n_books]; segm_tok i64 [B, T] (or [B*T]) parsing
+    labels of the token cells.  Returns (cost f64 [B, 3, n_books], count i32 [B, 3], attr i64 [B, 3]); the groups
+    are upper, lower, outer."""
+    _chk_f32(dmin)
+    _chk_i64(segm_tok)
+    assert dmin.dim() == 2 and dmin.is_contiguous()
+    n, nb = dmin.shape
+    assert B > 0 and n % B == 0 and segm_tok.numel() == n, (B, n, segm_tok.numel())
+    cost = torch.empty((B, 3, nb), device=dmin.device, dtype=torch.float64)
+    count = torch.empty((B, 3), device=dmin.device, dtype=torch.int32)
+    attr = torch.empty((B, 3), device=dmin.device, dtype=torch.int64)
+    check(_lib.load().t2h_texture_vote(_p(dmin), _p(segm_tok), B, n // B, nb, _p(cost), _p(count), _p(attr),
+                                       _stream()), 't2h_texture_vote')
+    return cost, count, attr
+
+
 def codebook_gather_tex(idx_lists, tex, books):
     """idx_lists [18, n] i64, tex [n] i64, books [18, n_e, e_dim] -> [n, e_dim]."""
     _chk_i64(idx_lists, tex)
