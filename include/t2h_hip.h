@@ -749,6 +749,27 @@ int t2h_argmax_rows_f32(const float* x, int32_t ld, int64_t* out, int64_t rows,
  * mul(255).add(0.5).clamp(0,255) (models/sample_model.py:245-254) */
 int t2h_image_epilogue(const float* dec, int32_t ldd, float* img_nchw, uint8_t* img_u8,
                        int32_t B, int32_t HW, void* stream);
+/* Two-band compositing of an edited region into the source photo (opt-in, not in the reference).
+ *   dec    f32 [B][3][H][W] in [0, 1]: the NCHW image t2h_image_epilogue writes;
+ *   photo  f32 [B][3][H][W]; photo_signed != 0: in the encoders' [-1, 1] range, read as p = clamp((x + 1) / 2, 0, 1)
+ *          (the epilogue's formula, fp32), otherwise p = x;
+ *   keep   uint8 [B][th * tw], 1 = kept cell, 0 = edited cell (t2h_region_keep); cell = H / th = W / tw, a whole number;
+ *   taps   f32 [2R + 1], 0 <= R <= 32: the blur's weights (the caller's Gaussian of sigma = r_lo / 4, sum 1);
+ *   r_hi, r_lo: 1 <= r_hi <= r_lo <= 64, the widths in pixels over which fine detail and the colour offset fade.
+ * d[b][y][x] = Chebyshev distance in pixels from (y, x) to the nearest pixel of an edited cell of image b (0 inside an
+ * edited cell; cell (r, c) covers rows cell r .. cell r + cell - 1 and the columns likewise; +inf without an edited
+ * cell).  w_hi = max(0, 1 - d / r_hi), w_lo = max(0, 1 - d / r_lo), diff = dec - p, low = diff blurred with taps along
+ * W, then along H, coordinates clamped to the image (replicate).
+ *   d == 0:     out = dec, the input's bits;
+ *   d >= r_lo:  out = p, its bits;
+ *   otherwise:  out = clamp(p + w_lo low + w_hi (diff - low), 0, 1).
+ * out f32 [B][3][H][W] (must not alias dec / photo); out_u8 (may be NULL) uint8 [B][H][W][3] = out * 255 + 0.5 clamped
+ * to 0 .. 255 and truncated, the epilogue's rule.  One launch, one workgroup per 32 x 32 tile of one image; a tile
+ * farther than r_lo from every edited cell copies p without reading dec, a tile inside edited cells copies dec, low
+ * lives in LDS only.  An image's output is a function of that image alone.  H, W need not be multiples of 32 or 4. */
+int t2h_composite_region_f32(const float* dec, const float* photo, const uint8_t* keep, const float* taps,
+                             float* out, uint8_t* out_u8, int32_t B, int32_t H, int32_t W, int32_t th, int32_t tw,
+                             int32_t r_hi, int32_t r_lo, int32_t R, int32_t photo_signed, void* stream);
 /* ShapeAttrEmbedding.forward (models/archs/shape_attr_embedding_arch.py:23-35).
  * w0t: first-layer weights transposed and stacked [sum(cls_num), dim] with
  * cls_off[a] = first row of attribute a; b0 [n_attr,dim]; w1 [n_attr,dim,dim];

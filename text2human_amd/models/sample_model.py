@@ -534,17 +534,25 @@ class BaseSampleModel():
     @torch.no_grad()
     def edit_and_refine(self, top_indices_list, region=None, labels=None, bot_indices_list=None, save_dir=None,
                         img_name=None, order='random', rounds=None, choice_temp=4.5, top_k=None, top_p=None, temp=1.0,
-                        refine_temp=None, refine_top_k=None, refine_top_p=None):
+                        refine_temp=None, refine_top_k=None, refine_top_p=None, source_image=None, blend_hi=4,
+                        blend_lo=32):
         """Region edit end to end: resample the top tokens of the region (region_keep), predict the bottom indices,
         keep `bot_indices_list` (e.g. a photo's bot_encode) outside the region if given, decode.  Return values and
         files follow sample_and_refine: with save_dir and img_name both None the first image f32 [1, 3, H, W];
         otherwise {save_dir}/{img_name[i]} PNGs are written and their uint8 [B, H, W, 3] pixels returned.  The edited
         index lists are left in self.edit_top_indices_list / self.edit_bot_indices_list (18 x int64 [B, 512]).
         refine_temp / refine_top_k / refine_top_p: the bottom indices are drawn (decode_indices); kept tokens keep
-        theirs whatever these are."""
+        theirs whatever these are.  source_image: the photo the index lists were encoded from, f32
+        [B, 3, H, W] in [-1, 1] (what hier.encode_photo took) -- the image returned and written is then
+        composite(decoded, source_image, keep, blend_hi, blend_lo): the decoder's pixels inside the edited cells, the
+        photo's own farther than blend_lo pixels from them.  The keep mask is left in self.edit_keep (uint8 [B, 512]) so
+        that composite can be called again with other radii; sampling and the index lists are the same either way."""
         refine_kw = dict(refine_temp=refine_temp, refine_top_k=refine_top_k, refine_top_p=refine_top_p)
         options.refine_values(refine_temp, refine_top_k, refine_top_p, batch=self.batch_size)  # (before anything is drawn)
+        if source_image is not None:
+            source_image = self._composite_source(source_image, self.batch_size, blend_hi, blend_lo)
         keep = self.region_keep(region, labels)
+        self.edit_keep = keep
         keep_rows = keep.reshape(-1).contiguous()
         bot = None
         if bot_indices_list is not None:
@@ -567,11 +575,47 @@ class BaseSampleModel():
             finally:
                 self.batch_size, self.texture_mask = keep_b, keep_mask
             self._edit_results(top, inter, 1)
+            if source_image is not None:
+                img, _ = ops.composite_region(img, source_image[:1], keep[:1], self.shape, r_hi=blend_hi, r_lo=blend_lo)
             return img
-        _, u8, inter = self.decode_indices(top, want_u8=True, return_inter=True, bot_keep=bot_keep, **refine_kw)
+        img, u8, inter = self.decode_indices(top, want_u8=True, return_inter=True, bot_keep=bot_keep, **refine_kw)
         self._edit_results(top, inter, self.batch_size)
+        if source_image is not None:
+            _, u8 = ops.composite_region(img, source_image, keep, self.shape, r_hi=blend_hi, r_lo=blend_lo, want_u8=True)
         save_u8_images(u8, save_dir, img_name)
         return u8
+
+    def _composite_source(self, source_image, b, blend_hi, blend_lo):
+        """checks of composite / edit_and_refine(source_image=...) -> the photo on the device, f32, contiguous"""
+        ops._check_composite_radii(blend_hi, blend_lo, names=('blend_hi', 'blend_lo'))
+        hh, ww = self.texture_mask.shape[2], self.texture_mask.shape[3]
+        if not torch.is_tensor(source_image) or tuple(source_image.shape) != (b, 3, hh, ww):
+            got = tuple(source_image.shape) if torch.is_tensor(source_image) else type(source_image).__name__
+            raise ValueError(f'source_image must be [{b}, 3, {hh}, {ww}] (the photo the indices were encoded from, in '
+                             f'[-1, 1]), got {got}')
+        return source_image.to(self.device, torch.float32).contiguous()
+
+    @torch.no_grad()
+    def composite(self, img, source_image, keep, blend_hi=4, blend_lo=32, want_u8=False):
+        """Pastes a decoded edit back into its photo (ops.composite_region).  img: f32 [B, 3, H, W] in
+        [0, 1] from decode_indices / edit_and_refine (not an upscale=True image); source_image: the photo, f32
+        [B, 3, H, W] in [-1, 1]; keep: uint8 [B, 512] (region_keep, or self.edit_keep after edit_and_refine).
+        -> (img f32 [B, 3, H, W], u8 [B, H, W, 3] or None): img's pixels inside the edited cells, the photo's
+        ((x + 1) / 2).clamp(0, 1) farther than blend_lo pixels from them, both bit for bit; in between the photo plus
+        the decoder's low-frequency offset fading over blend_lo pixels and its fine detail over blend_hi."""
+        b = self.batch_size
+        src = self._composite_source(source_image, b, blend_hi, blend_lo)
+        if not torch.is_tensor(img) or tuple(img.shape) != tuple(src.shape):
+            got = tuple(img.shape) if torch.is_tensor(img) else type(img).__name__
+            raise ValueError(f'img must be [{b}, 3, {src.shape[2]}, {src.shape[3]}] like the source image (upscale=True '
+                             f'images are not composited), got {got}')
+        n_tok = self.shape[0] * self.shape[1]
+        if not torch.is_tensor(keep) or tuple(keep.shape) != (b, n_tok):
+            got = tuple(keep.shape) if torch.is_tensor(keep) else type(keep).__name__
+            raise ValueError(f'keep must be [{b}, {n_tok}], got {got}')
+        return ops.composite_region(img.to(self.device, torch.float32).contiguous(), src,
+                                    keep.to(self.device, torch.uint8).contiguous(), self.shape, r_hi=blend_hi,
+                                    r_lo=blend_lo, want_u8=want_u8)
 
     def _edit_results(self, top, inter, b):
         bot = torch.cat([d['bot_lists'] for d in inter], 1) if len(inter) > 1 else inter[0]['bot_lists']

@@ -1556,6 +1556,60 @@ def image_epilogue(dec, B, H, W, want_u8=False):
     return img, u8
 
 
+COMPOSITE_R_MAX = 32  # widest blur radius of t2h_composite_region_f32 (taps [2R + 1])
+_composite_taps = {}
+
+
+def composite_taps_host(r_lo):
+    """The blur of ops.composite_region -> float32 numpy [2R + 1]: a Gaussian of sigma = r_lo / 4 cut at
+    R = min(32, ceil(3 sigma)), computed and normalised to sum 1 in float64, then rounded to fp32."""
+    sigma = int(r_lo) / 4.0
+    R = min(COMPOSITE_R_MAX, int(np.ceil(3.0 * sigma)))
+    k = np.arange(-R, R + 1, dtype=np.float64)
+    g = np.exp(-0.5 * (k / sigma) ** 2)
+    return (g / g.sum()).astype(np.float32)
+
+
+def _check_composite_radii(r_hi, r_lo, names=('r_hi', 'r_lo')):
+    for name, v in zip(names, (r_hi, r_lo)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+            raise ValueError(f'compositing: {name} must be an integer number of pixels, got {v!r}')
+    if not 1 <= r_hi <= r_lo <= 64:
+        raise ValueError(f'compositing: need 1 <= {names[0]} <= {names[1]} <= 64, got {names[0]}={r_hi}, '
+                         f'{names[1]}={r_lo}')
+
+
+def composite_region(dec, photo, keep, cells, r_hi=4, r_lo=32, photo_signed=True, want_u8=False):
+    """Two-band compositing of an edited region into its source photo (t2h_composite_region_f32).
+    dec f32 [B, 3, H, W] in [0, 1] (image_epilogue's image), photo f32 [B, 3, H, W] (photo_signed: in [-1, 1], read as
+    ((x + 1) / 2).clamp(0, 1)), keep uint8 [B, th * tw] (region_keep: 0 = edited cell), cells = (th, tw).  With d the
+    Chebyshev distance of a pixel to the nearest edited cell: the decoder's pixels where d == 0, the photo's where
+    d >= r_lo, in between the photo plus the decoder's blurred offset fading over r_lo pixels and its detail over r_hi.
+    -> (img f32 [B, 3, H, W], u8 [B, H, W, 3] or None).  No host synchronisation, the generator is not touched."""
+    _chk_f32(dec, photo)
+    _check_composite_radii(r_hi, r_lo)
+    if dec.dim() != 4 or dec.shape[1] != 3 or not dec.is_contiguous():
+        raise ValueError(f'composite_region: dec must be a contiguous [B, 3, H, W] image, got {tuple(dec.shape)}')
+    if tuple(photo.shape) != tuple(dec.shape) or not photo.is_contiguous():
+        raise ValueError(f'composite_region: photo must be contiguous and shaped like dec {tuple(dec.shape)}, got '
+                         f'{tuple(photo.shape)}')
+    B, _, H, W = dec.shape
+    th, tw = cells
+    if tuple(keep.shape) != (B, th * tw):
+        raise ValueError(f'composite_region: keep must be [{B}, {th * tw}], got {tuple(keep.shape)}')
+    _chk_u8(keep, B * th * tw)
+    key = (int(r_lo), dec.device)
+    taps = _composite_taps.get(key)
+    if taps is None:  # (built once per r_lo and device, outside any capture)
+        taps = _composite_taps[key] = torch.from_numpy(composite_taps_host(r_lo)).to(dec.device)
+    img = torch.empty_like(dec)
+    u8 = torch.empty((B, H, W, 3), device=dec.device, dtype=torch.uint8) if want_u8 else None
+    check(_lib.load().t2h_composite_region_f32(_p(dec), _p(photo), _p(keep), _p(taps), _p(img), _p(u8), B, H, W, th, tw,
+                                               int(r_hi), int(r_lo), (taps.numel() - 1) // 2, int(bool(photo_signed)),
+                                               _stream()), 't2h_composite_region_f32')
+    return img, u8
+
+
 def texture_map(segm, upper, lower, outer):
     """segm i64 [B,1,H,W] -> f32 mask [B,1,H,W]."""
     _chk_i64(segm, upper, lower, outer)
