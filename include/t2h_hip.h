@@ -770,6 +770,45 @@ int t2h_image_epilogue(const float* dec, int32_t ldd, float* img_nchw, uint8_t* 
 int t2h_composite_region_f32(const float* dec, const float* photo, const uint8_t* keep, const float* taps,
                              float* out, uint8_t* out_u8, int32_t B, int32_t H, int32_t W, int32_t th, int32_t tw,
                              int32_t r_hi, int32_t r_lo, int32_t R, int32_t photo_signed, void* stream);
+/* Garment colour control in image space (opt-in, not in the reference): the colour statistics of
+ * parsing-map regions, and a recolouring that moves a region's statistics onto a target's.
+ *   img        f32 [B][3][H][W]; img_signed != 0: in the encoders' [-1, 1] range, read as p = clamp((x + 1) / 2, 0, 1)
+ *              (the epilogue's formula, fp32), otherwise p = x;
+ *   segm       f32 [B][H][W], the parsing map as the tokenizer reads it;
+ *   label_bits uint64 [G] in HOST memory, 1 <= G <= 4, shared by the batch: group g = the labels whose bit is set.
+ *              Membership m_g of a pixel follows mode 2 of t2h_region_keep: v = segm is a member iff 0 <= v < 64, v is
+ *              a whole number and bit (int)v of label_bits[g] is set; every other value (negative, >= 64, fractional,
+ *              NaN, inf) is in no group.  The groups must be disjoint (-1 otherwise).
+ * Colour space, fp32, one device function for both entry points: Y = 0.299 R + 0.587 G + 0.114 B, U = B - Y, V = R - Y;
+ * inverse R = Y + V, B = Y + U, G = Y - (0.299 V + 0.114 U) / 0.587.
+ *
+ * t2h_region_color_stats: stats f64 [B][G][8] = {n, mY, mU, mV, sY, sU, sV, 0}: n the member count, m the means over
+ * the members, s the population standard deviations sqrt(max(0, E[x^2] - m^2)); n == 0: eight zeros.  Y / U / V of a
+ * pixel are formed in fp32, widened and summed in f64 in a fixed order (per lane in ascending address order, a fixed
+ * butterfly per wave, waves and stripes in ascending order; no floating-point atomics): two calls give the same bits,
+ * and image b's row is a function of image b alone.  partial: caller's workspace, f64 [B][ceil(H / 16)][G][8] (one row
+ * per image, stripe of 16 image rows and group), fully overwritten.  Two launches.
+ *
+ * t2h_recolor_region_f32: src_stats / dst_stats f64 [B][G][8] (device) as above: the region's own statistics s and the
+ * target's t; 0 <= luma <= 1; 1 <= gain_max <= 16; 0 <= feather <= 8 pixels.  Per (b, g), formed in f64 and rounded
+ * once to fp32: gain_c = clamp(t.s_c / s.s_c, 1 / gain_max, gain_max) if s.s_c > 1e-6 and t.s_c > 0, else 1
+ * (c = Y, U, V); s.mY, s.mU, s.mV; luma (t.mY - s.mY); t.mU; t.mV.  Per pixel in fp32:
+ *   Y' = s.mY + gain_Y (Y - s.mY) + luma (t.mY - s.mY),  U' = t.mU + gain_U (U - s.mU),  V' likewise,
+ *   T_g(p) = the inverse transform of (Y', U', V').
+ * A group with s.n == 0 or t.n == 0 is inactive in that image: it has no members there.  With f = feather,
+ *   N_g(y, x) = sum over |i| <= f, |j| <= f of (f + 1 - |i|)(f + 1 - |j|) m_g(clampH(y + i), clampW(x + j))
+ * (an integer, replicate borders, integer arithmetic) and alpha_g = N_g / (f + 1)^4:
+ *   out = p, its bits, where every N_g of an active group is 0 (no member within Chebyshev distance f);
+ *   out = clamp(p + sum_g alpha_g (T_g(p) - p), 0, 1) elsewhere, g ascending.
+ * out f32 [B][3][H][W] (must not alias img); out_u8 (may be NULL) uint8 [B][H][W][3] = out * 255 + 0.5 clamped to
+ * 0 .. 255 and truncated, the epilogue's rule.  One launch, one workgroup per 32 x 32 tile of one image; a tile without
+ * a member in its halo copies p, a tile whose halo is one group takes alpha = 1 without filtering, both with the bits
+ * of the general path.  An image's output is a function of that image alone.  H, W need not be multiples of 32 or 4. */
+int t2h_region_color_stats(const float* img, int32_t img_signed, const float* segm, const uint64_t* label_bits,
+                           int32_t G, int32_t B, int32_t H, int32_t W, double* partial, double* stats, void* stream);
+int t2h_recolor_region_f32(const float* img, int32_t img_signed, const float* segm, const uint64_t* label_bits,
+                           int32_t G, const double* src_stats, const double* dst_stats, float luma, float gain_max,
+                           int32_t feather, float* out, uint8_t* out_u8, int32_t B, int32_t H, int32_t W, void* stream);
 /* ShapeAttrEmbedding.forward (models/archs/shape_attr_embedding_arch.py:23-35).
  * w0t: first-layer weights transposed and stacked [sum(cls_num), dim] with
  * cls_off[a] = first row of attribute a; b0 [n_attr,dim]; w1 [n_attr,dim,dim];

@@ -198,6 +198,25 @@ def with_revision(opt, passes=0, fraction=None, folds=None):
     return opt
 
 
+def with_recolor(opt, upper=None, lower=None, outer=None, feather=None, luma=None):
+    """`opt` with the keys that make sample_and_refine / edit_and_refine / inference recolour the garments of the image
+    they return and write (options.recolor_settings; an image-space operator): upper / lower / outer an
+    (r, g, b) in [0, 1] or None; all three None: off, the keys are removed; feather / luma None: their defaults.
+    Returns opt."""
+    from . import options
+    for key in ('recolor_upper', 'recolor_lower', 'recolor_outer', 'recolor_feather', 'recolor_luma'):
+        opt.pop(key, None)
+    colours = {n: v for n, v in zip(options.RECOLOR_NAMES, (upper, lower, outer)) if v is not None}
+    if colours:
+        for n, v in colours.items():
+            opt[f'recolor_{n}'] = list(options.recolor_colour(v, f'recolor_{n}'))
+        if feather is not None:
+            opt['recolor_feather'] = options.recolor_feather_value(feather)
+        if luma is not None:
+            opt['recolor_luma'] = options.recolor_luma_value(luma)
+    return opt
+
+
 def write_yaml(opt, path):
     with open(path, 'w') as f:
         yaml.safe_dump(dict(opt), f, sort_keys=False)

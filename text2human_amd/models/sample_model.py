@@ -549,6 +549,7 @@ class BaseSampleModel():
         that composite can be called again with other radii; sampling and the index lists are the same either way."""
         refine_kw = dict(refine_temp=refine_temp, refine_top_k=refine_top_k, refine_top_p=refine_top_p)
         options.refine_values(refine_temp, refine_top_k, refine_top_p, batch=self.batch_size)  # (before anything is drawn)
+        recolor = options.recolor_settings(self.opt)  # (options: recolor_*; None: off; DESIGN.md 4.6l)
         if source_image is not None:
             source_image = self._composite_source(source_image, self.batch_size, blend_hi, blend_lo)
         keep = self.region_keep(region, labels)
@@ -575,11 +576,15 @@ class BaseSampleModel():
             finally:
                 self.batch_size, self.texture_mask = keep_b, keep_mask
             self._edit_results(top, inter, 1)
+            if recolor is not None:  # (before the paste: the photo outside the edit keeps its pixels)
+                img, _ = self._recolor_by_options(img, recolor, first=1)
             if source_image is not None:
                 img, _ = ops.composite_region(img, source_image[:1], keep[:1], self.shape, r_hi=blend_hi, r_lo=blend_lo)
             return img
         img, u8, inter = self.decode_indices(top, want_u8=True, return_inter=True, bot_keep=bot_keep, **refine_kw)
         self._edit_results(top, inter, self.batch_size)
+        if recolor is not None:
+            img, u8 = self._recolor_by_options(img, recolor, want_u8=True)
         if source_image is not None:
             _, u8 = ops.composite_region(img, source_image, keep, self.shape, r_hi=blend_hi, r_lo=blend_lo, want_u8=True)
         save_u8_images(u8, save_dir, img_name)
@@ -616,6 +621,95 @@ class BaseSampleModel():
         return ops.composite_region(img.to(self.device, torch.float32).contiguous(), src,
                                     keep.to(self.device, torch.uint8).contiguous(), self.shape, r_hi=blend_hi,
                                     r_lo=blend_lo, want_u8=want_u8)
+
+    # ---- garment colour control: an image-space operator on a decoded image and the current parsing
+    # map.  Tokens, index lists and the generator are what they were.
+    def _recolor_inputs(self, img, name):
+        """-> (img f32 contiguous on the device, segm f32 [B, H, W]) of garment_colors / recolor"""
+        segm = self.segm.to(self.device, torch.float32)
+        b, hh, ww = segm.shape[0], segm.shape[-2], segm.shape[-1]
+        segm = segm.reshape(b, hh, ww).contiguous()
+        if not torch.is_tensor(img) or tuple(img.shape) != (b, 3, hh, ww):
+            got = tuple(img.shape) if torch.is_tensor(img) else type(img).__name__
+            raise ValueError(f'{name}: img must be [{b}, 3, {hh}, {ww}] like the parsing map (upscale=True images are not '
+                             f'recoloured), got {got}')
+        return img.to(self.device, torch.float32).contiguous(), segm
+
+    @torch.no_grad()
+    def garment_colors(self, img):
+        """What colour did it draw?  img: f32 [B, 3, H, W] in [0, 1] (decode_indices / sample_and_refine).  -> dict of
+        'upper' / 'lower' / 'outer': (rgb f32 [B, 3], count int64 [B]) on the device, over the pixels of that garment in
+        the current self.segm (ops.region_color_stats): rgb is the inverse transform of the mean (Y, U, V), zeros where
+        count is 0."""
+        img, segm = self._recolor_inputs(img, 'garment_colors')
+        names = list(options.RECOLOR_NAMES)
+        st = ops.region_color_stats(img, segm, names)
+        return {n: (ops.recolor_rgb(st[:, g, 1:4]).to(torch.float32), st[:, g, 0].to(torch.int64))
+                for g, n in enumerate(names)}
+
+    @torch.no_grad()
+    def recolor(self, img, upper=None, lower=None, outer=None, labels=None, like=None, luma=1.0, gain_max=4.0, feather=2,
+                want_u8=False):
+        """The same outfit, a garment in another colour (ops.recolor_region) -- an operator on the
+        decoded image, not a new sample.  img: f32 [B, 3, H, W] in [0, 1]; upper / lower / outer: an (r, g, b) in
+        [0, 1] or a [B, 3] tensor (one colour per image) for the garment of that name in the current self.segm;
+        labels = {'name': ([ids], colour)} adds a group of explicit parsing labels.  The garment's mean colour moves to
+        the target (its luma by the share `luma`), its pattern and shading stay; the change fades over `feather` pixels.
+        like = (image f32 [B or 1, 3, H, W] in [-1, 1], its parsing map): the target of every group named (value True)
+        is the statistics of the same group in that image -- mean and, within [1 / gain_max, gain_max], contrast.  A
+        group absent from an image (or from `like`) leaves that image untouched there; pixels farther than `feather`
+        from every group keep their bits.  -> (img f32 [B, 3, H, W], u8 [B, H, W, 3] or None)."""
+        img, segm = self._recolor_inputs(img, 'recolor')
+        b = img.shape[0]
+        named = [(n, ops.RECOLOR_GROUPS[n], v) for n, v in zip(options.RECOLOR_NAMES, (upper, lower, outer)) if v is not None]
+        for n, entry in (labels or {}).items():
+            if not isinstance(entry, (tuple, list)) or len(entry) != 2:
+                raise ValueError(f'recolor: labels[{n!r}] must be ([label ids], colour), got {entry!r}')
+            named.append((n, entry[0], entry[1]))
+        if not named:
+            raise ValueError('recolor: name at least one group (upper / lower / outer / labels)')
+        groups = [ids for _, ids, _ in named]
+        ops.recolor_group_bits(groups)
+        ops._check_recolor_params(luma, gain_max, feather)
+        if like is not None:
+            if any(v is not True for _, _, v in named):
+                raise ValueError('recolor: with like=(image, segm) a group is named by True, its target comes from that image')
+            if not isinstance(like, (tuple, list)) or len(like) != 2 or not all(torch.is_tensor(t) for t in like):
+                raise ValueError('recolor: like must be (image [B or 1, 3, H, W] in [-1, 1], its parsing map)')
+            ex = like[0].to(self.device, torch.float32).contiguous()
+            if ex.dim() != 4 or ex.shape[0] not in (1, b) or ex.shape[1] != 3 or like[1].numel() != ex.shape[0] * ex.shape[2] * ex.shape[3]:
+                raise ValueError(f'recolor: like must be (image [{b} or 1, 3, H, W], a parsing map of its size), got '
+                                 f'{tuple(like[0].shape)} and {tuple(like[1].shape)}')
+            ex_segm = like[1].to(self.device, torch.float32).reshape(ex.shape[0], ex.shape[2], ex.shape[3]).contiguous()
+            dst = ops.region_color_stats(ex, ex_segm, groups, img_signed=True).expand(b, -1, -1).contiguous()
+            src = ops.region_color_stats(img, segm, groups)
+        else:
+            colours = []
+            for n, _, v in named:
+                if torch.is_tensor(v):
+                    if tuple(v.shape) != (b, 3):
+                        raise ValueError(f'recolor: the colours of {n} must be [{b}, 3], got {tuple(v.shape)}')
+                    colours.append(v.to(self.device, torch.float64))
+                else:
+                    c = options.recolor_colour(v, f'recolor ({n})')
+                    colours.append(torch.tensor(c, dtype=torch.float64, device=self.device).expand(b, 3))
+            src = ops.region_color_stats(img, segm, groups)
+            dst = src.clone()  # (n and the deviations are the source's: gains 1, an absent group stays absent)
+            dst[:, :, 1:4] = ops.recolor_yuv(torch.stack(colours, 1))
+        return ops.recolor_region(img, segm, groups, src, dst, luma=luma, gain_max=gain_max, feather=feather,
+                                  want_u8=want_u8)
+
+    def _recolor_by_options(self, img, settings, first=None, want_u8=False):
+        """the options `recolor_*` (options.recolor_settings) on a decoded image; first: the image is the first `first`
+        images of the batch"""
+        colours, feather, luma = settings
+        keep_segm = self.segm
+        if first is not None:
+            self.segm = self.segm[:first]
+        try:
+            return self.recolor(img, luma=luma, feather=feather, want_u8=want_u8, **colours)
+        finally:
+            self.segm = keep_segm
 
     def _edit_results(self, top, inter, b):
         bot = torch.cat([d['bot_lists'] for d in inter], 1) if len(inter) > 1 else inter[0]['bot_lists']
@@ -798,6 +892,7 @@ class BaseSampleModel():
         refine_kw = self._refine_options()  # (options: refine_temp / refine_top_k / refine_top_p)
         best_of = options.sampling_best_of(self.opt)  # (options: sample_best_of; 1: the calls below, as always)
         revise = options.revise_settings(self.opt)  # (options: revise_passes / revise_fraction / revise_folds; None: off)
+        recolor = options.recolor_settings(self.opt)  # (options: recolor_*; None: off -- the image is the decoder's)
         if best_of > 1:
             kw = dict(trunc, temp=1)
             if confidence is not None:
@@ -833,8 +928,12 @@ class BaseSampleModel():
                                              **self._refine_first_image(refine_kw))
             finally:
                 self.batch_size, self.texture_mask = keep_b, keep_mask
+            if recolor is not None:  # (options: recolor_upper / recolor_lower / recolor_outer)
+                img, _ = self._recolor_by_options(img, recolor, first=1)
             return img
-        _, u8 = self.decode_indices(sampled_top_indices_list, want_u8=True, **refine_kw)
+        img, u8 = self.decode_indices(sampled_top_indices_list, want_u8=True, **refine_kw)
+        if recolor is not None:
+            _, u8 = self._recolor_by_options(img, recolor, want_u8=True)
         save_u8_images(u8, save_dir, img_name)
 
     def _image_seeds(self, img_name):

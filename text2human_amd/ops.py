@@ -1610,6 +1610,118 @@ def composite_region(dec, photo, keep, cells, r_hi=4, r_lo=32, photo_signed=True
     return img, u8
 
 
+RECOLOR_GROUPS = {'upper': (1, 4), 'lower': (3, 5, 21), 'outer': (2, )}  # the classes of t2h_texture_map
+RECOLOR_G_MAX, RECOLOR_FEATHER_MAX, RECOLOR_GAIN_MAX = 4, 8, 16.0
+RECOLOR_STRIPE = 16  # image rows per partial row of t2h_region_color_stats (its workspace: [B, ceil(H / 16), G, 8] f64)
+
+
+def recolor_group_bits(groups):
+    """groups of region_color_stats / recolor_region: 1 .. 4 entries, each a name of RECOLOR_GROUPS or an iterable of
+    parsing label ids in [0, 64), pairwise disjoint -> list of label bit sets (ValueError otherwise)."""
+    if isinstance(groups, (str, bytes)) or not hasattr(groups, '__len__') or not 1 <= len(groups) <= RECOLOR_G_MAX:
+        raise ValueError(f'recolor: groups must be a list of 1 .. {RECOLOR_G_MAX} group names or label lists, got {groups!r}')
+    out = []
+    for grp in groups:
+        if isinstance(grp, str):
+            if grp not in RECOLOR_GROUPS:
+                raise ValueError(f'recolor: unknown group {grp!r} (names: {sorted(RECOLOR_GROUPS)}; or give label ids)')
+            grp = RECOLOR_GROUPS[grp]
+        try:
+            labels = list(grp)
+        except TypeError:
+            raise ValueError(f'recolor: a group is a name or a list of label ids, got {grp!r}') from None
+        bits = 0
+        for lb in labels:
+            if isinstance(lb, bool) or not isinstance(lb, numbers.Integral) or not 0 <= int(lb) < 64:
+                raise ValueError(f'recolor: label ids must be integers in [0, 64), got {lb!r}')
+            bits |= 1 << int(lb)
+        if bits == 0:
+            raise ValueError('recolor: a group needs at least one label id')
+        if any(bits & b for b in out):
+            raise ValueError(f'recolor: the groups must be disjoint, {labels} shares a label with an earlier group')
+        out.append(bits)
+    return out
+
+
+def _check_recolor_params(luma, gain_max, feather):
+    if isinstance(feather, bool) or not isinstance(feather, numbers.Integral) or not 0 <= feather <= RECOLOR_FEATHER_MAX:
+        raise ValueError(f'recolor: feather must be an integer number of pixels in [0, {RECOLOR_FEATHER_MAX}], got {feather!r}')
+    if isinstance(luma, bool) or not isinstance(luma, numbers.Real) or not 0.0 <= float(luma) <= 1.0:
+        raise ValueError(f'recolor: luma must lie in [0, 1], got {luma!r}')
+    if isinstance(gain_max, bool) or not isinstance(gain_max, numbers.Real) or not 1.0 <= float(gain_max) <= RECOLOR_GAIN_MAX:
+        raise ValueError(f'recolor: gain_max must lie in [1, {RECOLOR_GAIN_MAX:g}], got {gain_max!r}')
+
+
+def _recolor_inputs(name, img, segm):
+    _chk_f32(img, segm)
+    if img.dim() != 4 or img.shape[1] != 3 or not img.is_contiguous():
+        raise ValueError(f'{name}: img must be a contiguous [B, 3, H, W] image, got {tuple(img.shape)}')
+    B, _, H, W = img.shape
+    if tuple(segm.shape) not in ((B, H, W), (B, 1, H, W)) or not segm.is_contiguous():
+        raise ValueError(f'{name}: segm must be a contiguous [{B}, {H}, {W}] (or [{B}, 1, {H}, {W}]) parsing map, got '
+                         f'{tuple(segm.shape)}')
+    return B, H, W
+
+
+def region_color_stats(img, segm, groups, img_signed=False):
+    """Colour statistics of parsing-map regions (t2h_region_color_stats).  img f32 [B, 3, H, W]
+    (img_signed: in [-1, 1], read as ((x + 1) / 2).clamp(0, 1)), segm f32 [B, H, W] or [B, 1, H, W] (the parsing map as
+    the tokenizer reads it), groups: see recolor_group_bits.  -> f64 [B, G, 8] on the device =
+    {n, mY, mU, mV, sY, sU, sV, 0} per image and group in the opponent space Y = 0.299 R + 0.587 G + 0.114 B,
+    U = B - Y, V = R - Y; n == 0: zeros.  Fixed summation order: the same bits on every call, an image's row does not
+    depend on its batch.  No host synchronisation."""
+    bits = recolor_group_bits(groups)
+    B, H, W = _recolor_inputs('region_color_stats', img, segm)
+    G = len(bits)
+    partial = torch.empty((B, (H + RECOLOR_STRIPE - 1) // RECOLOR_STRIPE, G, 8), device=img.device, dtype=torch.float64)
+    stats = torch.empty((B, G, 8), device=img.device, dtype=torch.float64)
+    check(_lib.load().t2h_region_color_stats(_p(img), int(bool(img_signed)), _p(segm), (ctypes.c_uint64 * G)(*bits), G, B, H,
+                                             W, _p(partial), _p(stats), _stream()), 't2h_region_color_stats')
+    return stats
+
+
+def recolor_region(img, segm, groups, src_stats, dst_stats, luma=1.0, gain_max=4.0, feather=2, img_signed=False,
+                   want_u8=False):
+    """Moves the colour statistics of parsing-map regions onto targets (t2h_recolor_region_f32): an
+    image-space operator.  img / segm / groups as region_color_stats; src_stats f64 [B, G, 8]: region_color_stats of
+    this image; dst_stats f64 [B, G, 8]: the targets (another image's statistics, or src_stats with mY, mU, mV replaced
+    by a plain colour's -- the gains are then 1 and pattern and shading survive).  Per group U and V are re-centred on
+    the target's means and Y is shifted by luma (t.mY - s.mY); deviations are scaled by t.s / s.s within
+    [1 / gain_max, gain_max].  The change fades over `feather` pixels outside a region (a tent of integer weights);
+    pixels farther than that from every region keep their bits.  A group with n == 0 in either row leaves that image
+    untouched there.  -> (img f32 [B, 3, H, W] in [0, 1] where touched, u8 [B, H, W, 3] or None).  No host
+    synchronisation, the generator is not touched."""
+    bits = recolor_group_bits(groups)
+    _check_recolor_params(luma, gain_max, feather)
+    B, H, W = _recolor_inputs('recolor_region', img, segm)
+    G = len(bits)
+    for name, st in (('src_stats', src_stats), ('dst_stats', dst_stats)):
+        if not torch.is_tensor(st) or st.dtype != torch.float64 or st.device != img.device or \
+                tuple(st.shape) != (B, G, 8) or not st.is_contiguous():
+            got = (tuple(st.shape), st.dtype, st.device) if torch.is_tensor(st) else type(st).__name__
+            raise ValueError(f'recolor_region: {name} must be a contiguous float64 [{B}, {G}, 8] tensor on {img.device} '
+                             f'(region_color_stats), got {got}')
+    out = torch.empty_like(img)
+    u8 = torch.empty((B, H, W, 3), device=img.device, dtype=torch.uint8) if want_u8 else None
+    check(_lib.load().t2h_recolor_region_f32(_p(img), int(bool(img_signed)), _p(segm), (ctypes.c_uint64 * G)(*bits), G,
+                                             _p(src_stats), _p(dst_stats), float(luma), float(gain_max), int(feather),
+                                             _p(out), _p(u8), B, H, W, _stream()), 't2h_recolor_region_f32')
+    return out, u8
+
+
+def recolor_yuv(colour):
+    """(..., 3) RGB -> (..., 3) = (Y, U, V) of the recolouring's opponent space, float64 (a tensor stays on its device)"""
+    c = colour.to(torch.float64) if torch.is_tensor(colour) else torch.as_tensor(colour, dtype=torch.float64)
+    y = 0.299 * c[..., 0] + 0.587 * c[..., 1] + 0.114 * c[..., 2]
+    return torch.stack([y, c[..., 2] - y, c[..., 0] - y], -1)
+
+
+def recolor_rgb(yuv):
+    """the inverse of recolor_yuv: (..., 3) = (Y, U, V) -> (..., 3) RGB, in the input's dtype"""
+    y, u, v = yuv[..., 0], yuv[..., 1], yuv[..., 2]
+    return torch.stack([y + v, y - (0.299 * v + 0.114 * u) / 0.587, y + u], -1)
+
+
 def texture_map(segm, upper, lower, outer):
     """segm i64 [B,1,H,W] -> f32 mask [B,1,H,W]."""
     _chk_i64(segm, upper, lower, outer)

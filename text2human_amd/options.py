@@ -346,6 +346,55 @@ def revise_settings(opt):
     return (passes, fraction, folds) if passes > 0 else None
 
 
+# Garment colour control.  No `recolor_upper` / `recolor_lower` / `recolor_outer` key = off = today's run.
+RECOLOR_NAMES = ('upper', 'lower', 'outer')
+RECOLOR_FEATHER_DEFAULT, RECOLOR_FEATHER_MAX, RECOLOR_LUMA_DEFAULT = 2, 8, 1.0
+
+
+def recolor_colour(value, name='colour'):
+    """an (r, g, b) colour of the recolouring: three numbers in [0, 1] -> tuple of floats (ValueError otherwise)"""
+    import math
+    import numbers
+    if isinstance(value, (str, bytes)) or not hasattr(value, '__len__') or len(value) != 3:
+        raise ValueError(f'{name}: a colour is three numbers r, g, b in [0, 1], got {value!r}')
+    out = []
+    for v in value:
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or math.isnan(float(v)) or not 0.0 <= float(v) <= 1.0:
+            raise ValueError(f'{name}: a colour is three numbers r, g, b in [0, 1], got {value!r}')
+        out.append(float(v))
+    return tuple(out)
+
+
+def recolor_feather_value(feather):
+    import numbers
+    if isinstance(feather, bool) or not isinstance(feather, numbers.Integral) or not 0 <= int(feather) <= RECOLOR_FEATHER_MAX:
+        raise ValueError(f'recolor_feather: must be an integer number of pixels in [0, {RECOLOR_FEATHER_MAX}], got {feather!r}')
+    return int(feather)
+
+
+def recolor_luma_value(luma):
+    import math
+    import numbers
+    if isinstance(luma, bool) or not isinstance(luma, numbers.Real) or math.isnan(float(luma)) or not 0.0 <= float(luma) <= 1.0:
+        raise ValueError(f'recolor_luma: must lie in [0, 1], got {luma!r}')
+    return float(luma)
+
+
+def recolor_settings(opt):
+    """-> None (none of `recolor_upper` / `recolor_lower` / `recolor_outer` set: off) or (colours, feather, luma):
+    colours = {'upper': (r, g, b), ...} of the keys that are set, `recolor_feather` (default 2) and `recolor_luma`
+    (default 1.0), validated.  All five keys are validated whether the feature is on or not.  `opt` is not changed."""
+    colours = {}
+    for name in RECOLOR_NAMES:
+        v = opt.get(f'recolor_{name}')
+        if v is not None:
+            colours[name] = recolor_colour(v, f'recolor_{name}')
+    feather, luma = opt.get('recolor_feather'), opt.get('recolor_luma')
+    feather = recolor_feather_value(RECOLOR_FEATHER_DEFAULT if feather is None else feather)
+    luma = recolor_luma_value(RECOLOR_LUMA_DEFAULT if luma is None else luma)
+    return (colours, feather, luma) if colours else None
+
+
 def dict2str(opt, indent_level=1):
     msg = ''
     pad = ' ' * (indent_level * 2)

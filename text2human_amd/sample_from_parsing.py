@@ -133,7 +133,29 @@ def cli_parser():
     ap.add_argument('--revise-folds', type=int, choices=options.REVISE_FOLDS, default=None,
                     help='self-correction: folds of the critic\'s lattice = its evaluations per scoring (overrides '
                          'revise_folds; default 4)')
+    for name in options.RECOLOR_NAMES:
+        ap.add_argument(f'--recolor-{name}', type=_rgb, default=None, metavar='R,G,B',
+                        help=f'recolour the {name} garment of every image written towards this colour, three numbers in '
+                             f'[0, 1]: an image-space operator on the decoded image, the sampled tokens are what they '
+                             f'were (sets recolor_{name})')
+    ap.add_argument('--recolor-feather', type=int, default=None,
+                    help='recolouring: pixels over which the change fades outside a garment, 0 .. 8 (overrides '
+                         'recolor_feather; default 2)')
+    ap.add_argument('--recolor-luma', type=float, default=None,
+                    help='recolouring: share of the luma difference to the target colour that is applied, in [0, 1] '
+                         '(overrides recolor_luma; default 1)')
     return ap
+
+
+def _rgb(text):
+    """'R,G,B' -> [r, g, b] (floats; their range is checked by options.recolor_settings)"""
+    try:
+        vals = [float(x) for x in text.split(',')]
+    except ValueError:
+        vals = []
+    if len(vals) != 3:
+        raise argparse.ArgumentTypeError(f'expected three numbers R,G,B, got {text!r}')
+    return vals
 
 
 def apply_cli(opt, args):
@@ -145,7 +167,9 @@ def apply_cli(opt, args):
                    ('per_image_seeds', getattr(args, 'per_image_seeds', None)),
                    ('revise_passes', getattr(args, 'revise_passes', None)),
                    ('revise_fraction', getattr(args, 'revise_fraction', None)),
-                   ('revise_folds', getattr(args, 'revise_folds', None))):
+                   ('revise_folds', getattr(args, 'revise_folds', None)),
+                   *((f'recolor_{n}', getattr(args, f'recolor_{n}', None))
+                     for n in options.RECOLOR_NAMES + ('feather', 'luma'))):
         if v is not None:
             opt[key] = v
     options.sampling_order(opt)
@@ -154,6 +178,7 @@ def apply_cli(opt, args):
     options.refine_sampling(opt)
     options.per_image_seeding(opt)
     options.revise_settings(opt)
+    options.recolor_settings(opt)
     return opt
 
 
